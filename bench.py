@@ -12,6 +12,9 @@ forward + backward + optimizer step.  Weak scaling: each rank owns a full
 graph replica and processes its own batches; DDP all-reduce over RCCL/xGMI.
 
 Run:  python bench.py --gpus N --steps K --warmup W
+  --dump-outputs DIR  also writes the last timed step's results as .npy
+                      (same arguments => same inputs, run to run)
+  --full              reserved for secondary measurements (none today)
 Multi-GPU (driver):  python -m torch.distributed.run --nnodes=1
   --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 """
@@ -31,8 +34,18 @@ import torch.nn.functional as F
 def parse_args():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=300)
-    p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--steps", type=int, default=None,
+                   help="timed steps (default 300; 5 without a GPU)")
+    p.add_argument("--warmup", type=int, default=None,
+                   help="untimed warmup steps (default 20; 2 without a GPU)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step computed (loss, seed-node logits, seed ids, "
+                        "labels) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement or check. "
+                        "This benchmark has none besides the headline "
+                        "figure, so the flag currently adds nothing")
     p.add_argument("--batch-size", type=int, default=1024)
     p.add_argument("--fanout", type=str, default="15,10,5")
     p.add_argument("--nodes", type=int, default=2_449_029)
@@ -178,6 +191,7 @@ class _CapturedStep:
         self._graph = None
         self._warmups = 0
         self._loss = None
+        self._out = None
 
     def _load(self, data):
         nsn = [int(v) for v in data.num_sampled_nodes]
@@ -213,6 +227,7 @@ class _CapturedStep:
     def _run(self):
         self.opt.zero_grad(set_to_none=False)
         out = self.model(self.X, self.EI, self.nsn, self.nse)[:self.batch]
+        self._out = out
         loss = F.cross_entropy(out, self.Y)
         loss.backward()
         self.opt.step()
@@ -239,6 +254,51 @@ class _CapturedStep:
         return self._loss
 
 
+def dump_outputs(out_dir, last):
+    """Write what the last timed step computed as <out_dir>/<name>.npy.
+
+    loss and logits are what the step hands its caller; seed_nodes and
+    labels identify the batch they belong to (ids are exact in float64).
+    ~200 KB at the default config, so nothing needs sampling to stay
+    under the 64 MB budget.
+
+    Same arguments => same graph, features, initial weights, seed order
+    and sampled neighbourhoods.  main() also switches the segment
+    backward to its deterministic mode (glt_amd.ops.set_deterministic;
+    the result line says "deterministic": true): its atomics then add
+    grid-snapped, exactly summable terms, and the bias gradient is always
+    folded in fixed order.  That is order-independent as long as no dX
+    element collects more than 64x the largest |dY| of its layer; a hub
+    node sampled into that many neighbourhoods of one batch (possible
+    with --graph-skew) falls back to ordinary fp32 rounding for that
+    element.  Under that condition two runs of one build write identical
+    arrays (measured on MI355X, default graph, bf16 and fp32, after 10
+    and 120 steps: max |diff| 0).  Two different builds are a
+    different matter: any change in rounding is amplified by Adam step
+    by step (order-dependent atomics alone gave logits max |diff| 3e-3
+    after 10 steps and 3e-2 after 120), so compare builds at a small
+    --steps.
+    """
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    data = last["data"]
+    arrays = {
+        "loss": last["loss"].detach().float().reshape(1),
+        "logits": last["out"].detach().float(),
+        "labels": data.y[:data.batch_size].double(),
+    }
+    batch = getattr(data, "batch", None)
+    if batch is not None:
+        arrays["seed_nodes"] = batch.double()
+    total = 0
+    for name, t in arrays.items():
+        a = t.cpu().contiguous().numpy()
+        total += a.nbytes
+        assert total <= 64 * 2**20, "dump exceeds 64 MB"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse_args()
     rank = int(os.environ.get("RANK", 0))
@@ -248,8 +308,13 @@ def main():
         # CPU debug mode: shrink so it finishes quickly
         args.nodes = min(args.nodes, 20_000)
         args.edges = min(args.edges, 400_000)
-        args.steps = min(args.steps, 5)
-        args.warmup = min(args.warmup, 2)
+    # explicit --steps/--warmup are always honoured
+    if args.steps is None:
+        args.steps = 300 if has_gpu else 5
+    if args.warmup is None:
+        args.warmup = 20 if has_gpu else 2
+    if args.steps < 1:
+        sys.exit("--steps must be >= 1")
 
     local_rank = int(os.environ.get("LOCAL_RANK", rank))
     device = torch.device("cuda", local_rank) if has_gpu \
@@ -265,6 +330,11 @@ def main():
     from glt_amd import Dataset, NeighborLoader
     from glt_amd.data import Feature
     from glt_amd.models import GraphSAGE
+    from glt_amd.ops import set_deterministic
+
+    # same arguments must give the same outputs run to run: take the
+    # order-independent segment backward (not the library default)
+    set_deterministic(True)
 
     fanout = [int(x) for x in args.fanout.split(",")]
     graph, feats, labels = build_synthetic(args, device, rank)
@@ -325,6 +395,8 @@ def main():
             return torch.autocast("cuda", dtype=torch.bfloat16)
         return contextlib.nullcontext()
 
+    last = {}
+
     def one_step():
         nonlocal it
         try:
@@ -332,8 +404,11 @@ def main():
         except StopIteration:
             it = iter(loader)
             data = next(it)
+        last["data"] = data
         if captured is not None:
-            return captured.step(data)
+            last["loss"] = captured.step(data)
+            last["out"] = captured._out
+            return last["loss"]
         opt.zero_grad(set_to_none=True)
         with amp_ctx():
             out = model(data.x, data.edge_index, data.num_sampled_nodes,
@@ -341,6 +416,9 @@ def main():
             loss = F.cross_entropy(out.float(), data.y[:data.batch_size])
         loss.backward()
         opt.step()
+        # references only (no sync, no copy): --dump-outputs reads them
+        # after the timed loop
+        last["out"], last["loss"] = out, loss
         return loss
 
     # warmup
@@ -363,6 +441,8 @@ def main():
         elapsed = t.item()
 
     loader.shutdown()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     batches_per_sec = args.steps / elapsed * world
     ms_per_step = elapsed / args.steps * 1000.0
     # ogbn-products train split: 196,615 seeds -> epoch equivalent
@@ -382,6 +462,7 @@ def main():
             "dtype": "bf16" if (args.amp or args.dtype == "bf16")
                      else "fp32",
             "data": "synthetic",
+            "deterministic": True,
             "config": {
                 "model": "GraphSAGE(3x256)",
                 "global_batch": args.batch_size * world,

@@ -259,9 +259,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gat_multi_fwd", &hip_gat_multi_fwd);
   m.def("gat_multi_bwd", &hip_gat_multi_bwd);
   m.def("segment_mean_fwd", &hip_segment_mean_fwd);
-  m.def("segment_mean_bwd", &hip_segment_mean_bwd);
+  m.def("segment_mean_bwd", &hip_segment_mean_bwd, py::arg("dy"),
+        py::arg("col"), py::arg("offsets"), py::arg("n_src"),
+        py::arg("order_independent") = false);
   m.def("segment_mean_cat_fwd", &hip_segment_mean_cat_fwd);
-  m.def("segment_mean_cat_bwd", &hip_segment_mean_cat_bwd);
+  m.def("segment_mean_cat_bwd", &hip_segment_mean_cat_bwd, py::arg("dy"),
+        py::arg("col"), py::arg("offsets"), py::arg("n_src"),
+        py::arg("order_independent") = false);
 
   // Memory plumbing
   m.def("host_mapped_view", &host_mapped_view, py::arg("src"),

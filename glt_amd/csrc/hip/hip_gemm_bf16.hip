@@ -305,7 +305,8 @@ void gemm_kt_kernel(const __bf16* __restrict__ A,
                     const __bf16* __restrict__ B,
                     float* __restrict__ C,
                     float* __restrict__ db,
-                    int64_t Kb, int64_t M, int64_t N, int64_t k_per_z) {
+                    int64_t Kb, int64_t M, int64_t N, int64_t k_per_z,
+                    int64_t plane) {
   __shared__ __bf16 As[GBM][GBK + LDP];   // As[m][k]
   __shared__ __bf16 Bs[GBN][GBK + LDP];   // Bs[n][k]
 
@@ -414,7 +415,7 @@ void gemm_kt_kernel(const __bf16* __restrict__ A,
   // atomic contention on every output cell).
   const int c_col = lane & 15;
   const int c_row0 = (lane >> 4) * 4;
-  float* Cz = C + (int64_t)blockIdx.z * M * N;
+  float* Cz = C + (int64_t)blockIdx.z * plane;
 #pragma unroll
   for (int fi2 = 0; fi2 < 2; ++fi2) {
 #pragma unroll
@@ -440,9 +441,13 @@ void gemm_kt_kernel(const __bf16* __restrict__ A,
     }
     dbs[m_l][phase] = s;
     __syncthreads();
+    // per-chunk partial rows, plain stores into the tail of this chunk's
+    // plane (db = C + M * N, planes `plane` floats apart): the host's one
+    // sum(0) folds C and db together in a fixed order (atomics here made
+    // db, and through Adam the whole run, differ from run to run)
     if (tid < GBM && block_row + tid < M)
-      atomicAdd(&db[block_row + tid], dbs[tid][0] + dbs[tid][1] +
-                                          dbs[tid][2] + dbs[tid][3]);
+      db[(int64_t)blockIdx.z * plane + block_row + tid] =
+          dbs[tid][0] + dbs[tid][1] + dbs[tid][2] + dbs[tid][3];
   }
 }
 
@@ -460,7 +465,7 @@ void gemm_kt128_kernel(const __bf16* __restrict__ A,
                        float* __restrict__ C,
                        float* __restrict__ db,
                        int64_t Kb, int64_t M, int64_t N,
-                       int64_t k_per_z) {
+                       int64_t k_per_z, int64_t plane) {
   __shared__ __bf16 As[KBM][GBK + LDP];   // As[m][k]
   __shared__ __bf16 Bs[KBN][GBK + LDP];   // Bs[n][k]
 
@@ -561,7 +566,7 @@ void gemm_kt128_kernel(const __bf16* __restrict__ A,
 
   const int c_col = lane & 15;
   const int c_row0 = (lane >> 4) * 4;
-  float* Cz = C + (int64_t)blockIdx.z * M * N;
+  float* Cz = C + (int64_t)blockIdx.z * plane;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -585,8 +590,8 @@ void gemm_kt128_kernel(const __bf16* __restrict__ A,
     dbs[m_l][phase] = s;
     __syncthreads();
     if (tid < KBM && block_row + tid < M)
-      atomicAdd(&db[block_row + tid], dbs[tid][0] + dbs[tid][1] +
-                                          dbs[tid][2] + dbs[tid][3]);
+      db[(int64_t)blockIdx.z * plane + block_row + tid] =
+          dbs[tid][0] + dbs[tid][1] + dbs[tid][2] + dbs[tid][3];
   }
 }
 
@@ -701,15 +706,17 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> hip_gemm_kt_bf16(
   z = std::max<int64_t>(1, (Kb + k_per_z - 1) / k_per_z);
   c10::optional<torch::Tensor> db;
   float* db_p = nullptr;
-  if (with_db) {
-    db = torch::zeros({M}, A.options().dtype(torch::kFloat32));
-    db_p = db->data_ptr<float>();
-  }
   if (Kb == 0) {
+    if (with_db) db = torch::zeros({M}, A.options().dtype(torch::kFloat32));
     return {torch::zeros({M, N}, A.options().dtype(torch::kFloat32)), db};
   }
-  // z>1: per-chunk partial planes + one sum(0) (no output atomics)
-  auto P = torch::empty({z, M, N}, A.options().dtype(torch::kFloat32));
+  // z>1: per-chunk partial planes + one sum(0) (no output atomics).  A
+  // plane is C's [M, N] followed, with_db, by the chunk's db row [M]:
+  // every (chunk, m) db cell is stored exactly once, by the
+  // blockIdx.y == 0 block of that (m tile, chunk).
+  const int64_t plane = M * N + (with_db ? M : 0);
+  auto P = torch::empty({z, plane}, A.options().dtype(torch::kFloat32));
+  if (with_db) db_p = P.data_ptr<float>() + M * N;
   dim3 grid((uint32_t)m_t, (uint32_t)n_t, (uint32_t)z);
   if (big) {
     auto* kfn = with_db ? gemm_kt128_kernel<true>
@@ -717,16 +724,19 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> hip_gemm_kt_bf16(
     hipLaunchKernelGGL(kfn, grid, dim3(512), 0, current_stream(),
                        reinterpret_cast<const __bf16*>(Ac.data_ptr()),
                        reinterpret_cast<const __bf16*>(Bc.data_ptr()),
-                       P.data_ptr<float>(), db_p, Kb, M, N, k_per_z);
+                       P.data_ptr<float>(), db_p, Kb, M, N, k_per_z,
+                       plane);
   } else {
     auto* kfn = with_db ? gemm_kt_kernel<true> : gemm_kt_kernel<false>;
     hipLaunchKernelGGL(kfn, grid, dim3(256), 0, current_stream(),
                        reinterpret_cast<const __bf16*>(Ac.data_ptr()),
                        reinterpret_cast<const __bf16*>(Bc.data_ptr()),
-                       P.data_ptr<float>(), db_p, Kb, M, N, k_per_z);
+                       P.data_ptr<float>(), db_p, Kb, M, N, k_per_z,
+                       plane);
   }
-  auto C = z == 1 ? P.squeeze(0) : P.sum(0);
-  return {C, db};
+  auto flat = z == 1 ? P.squeeze(0) : P.sum(0);
+  if (with_db) db = flat.narrow(0, M * N, M);
+  return {flat.narrow(0, 0, M * N).view({M, N}), db};
 }
 
 torch::Tensor hip_mfma_bf16_selftest(const torch::Tensor& A,

@@ -6,6 +6,19 @@
  * atomics (same contention class as torch index_add_, but fused with the
  * degree division and vectorized).
  *
+ * Default backward: plain fp32 atomics, so low-order bits depend on the
+ * order in which they land.  order_independent = true (the python layer
+ * passes it in deterministic mode, see glt_amd/ops/segment.py) trades
+ * precision for run-to-run reproducibility: every contribution is first
+ * snapped to a common power-of-two grid q = 2^(e + kGridHeadroomBits - 24),
+ * 2^e > max|dY| (absmax pre-pass fused into the arena's zero fill), so
+ * each fp32 partial sum below 2^24 q = 2^kGridHeadroomBits * 2^e is exact
+ * and addition order cannot matter.  A dX element that collects more than
+ * that (>= 64x the largest |dY|) rounds like ordinary fp32 again and loses
+ * the guarantee.  Snapping costs up to q/2 <= 2^-18 max|dY| ABSOLUTE per
+ * term: terms far below max|dY| lose relative precision or vanish, which
+ * is why it is not the default.
+ *
  * Replaces the 4-kernel torch sequence (bincount + index_select +
  * index_add_ + div) in SAGEConv (glt_amd/models/layers.py).
  *
@@ -178,17 +191,82 @@ __global__ void seg_mean_cat_fwd_bf162_kernel(
   }
 }
 
+constexpr int kGridHeadroomBits = 6;
+
+// few, fat blocks: every backward wave folds all the parts before it starts
+constexpr int kMaxAmaxParts = 256;
+constexpr int kZeroBlock = 1024;
+
+// One launch in place of the arena's zero fill: zeroes arena[0, n_arena)
+// and leaves max |x| over this block's grid-stride share of x in
+// parts[blockIdx.x] (plain store; NaNs are skipped).  The backward
+// kernel folds the gridDim.x parts itself, so the absmax pre-pass costs
+// no launch of its own.
+template <typename scalar_t>
+__global__ void __launch_bounds__(kZeroBlock)
+zero_absmax_kernel(float* __restrict__ arena, int64_t n_arena,
+                   const scalar_t* __restrict__ x, int64_t n,
+                   float* __restrict__ parts) {
+  __shared__ float wm[kZeroBlock / kWave];
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t g0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  // allocator blocks are >= 16 B aligned and the arena starts one
+  const int64_t n4 = n_arena / 4;
+  float4* a4 = reinterpret_cast<float4*>(arena);
+  for (int64_t i = g0; i < n4; i += stride)
+    a4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int64_t i = n4 * 4 + g0; i < n_arena; i += stride) arena[i] = 0.f;
+  float m = 0.f;
+  for (int64_t i = g0; i < n; i += stride)
+    m = fmaxf(m, fabsf(static_cast<float>(x[i])));
+  for (int o = kWave / 2; o > 0; o >>= 1)
+    m = fmaxf(m, __shfl_xor(m, o, kWave));
+  if ((threadIdx.x & (kWave - 1)) == 0) wm[threadIdx.x / kWave] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kZeroBlock / kWave; ++w) m = fmaxf(m, wm[w]);
+    parts[blockIdx.x] = m;
+  }
+}
+
+// Magic constant 1.5 * 2^(e + kGridHeadroomBits - 1): (v + M) - M rounds
+// |v| <= max|dY| < 2^e to a multiple of ulp(M) = q.  0 = do not snap
+// (n_parts == 0: plain mode; empty / non-finite dY; q outside the normal
+// range).  Wave-uniform: every lane folds the same n_parts <=
+// kMaxAmaxParts block maxima.
+__device__ __forceinline__ float grid_magic(const float* __restrict__ parts,
+                                            int n_parts) {
+  float a = 0.f;
+  for (int i = threadIdx.x & (kWave - 1); i < n_parts; i += kWave)
+    a = fmaxf(a, parts[i]);
+  for (int o = kWave / 2; o > 0; o >>= 1)
+    a = fmaxf(a, __shfl_xor(a, o, kWave));
+  if (!(a > 0.f) || !isfinite(a)) return 0.f;
+  int e;
+  frexpf(a, &e);
+  const int me = e + kGridHeadroomBits - 1;
+  if (me > 120 || me < -100) return 0.f;
+  return ldexpf(1.5f, me);
+}
+
+__device__ __forceinline__ float snap(float v, float magic) {
+  return magic == 0.f ? v : __fsub_rn(__fadd_rn(v, magic), magic);
+}
+
 // dx[col[e], :] += dy[t, :] / deg(t)  (dx is always fp32)
 template <typename scalar_t>
 __global__ void seg_mean_bwd_kernel(const scalar_t* __restrict__ dy,
                                     const int64_t* __restrict__ col,
                                     const int64_t* __restrict__ off,
                                     int64_t n_tgt, int64_t feat,
+                                    const float* __restrict__ amax_parts,
+    int n_parts,
                                     float* __restrict__ dx) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t wave =
       (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
   const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const float magic = grid_magic(amax_parts, n_parts);
   for (int64_t t = wave; t < n_tgt; t += n_waves) {
     const int64_t s = off[t], e = off[t + 1];
     if (e <= s) continue;
@@ -197,7 +275,7 @@ __global__ void seg_mean_bwd_kernel(const scalar_t* __restrict__ dy,
       const int64_t c = col[k];
       for (int64_t f = lane; f < feat; f += kWave) {
         atomicAdd(&dx[c * feat + f],
-                  static_cast<float>(dy[t * feat + f]) * inv);
+                  snap(static_cast<float>(dy[t * feat + f]) * inv, magic));
       }
     }
   }
@@ -265,24 +343,27 @@ __global__ void seg_mean_cat_bwd_kernel(const scalar_t* __restrict__ dy,
                                         const int64_t* __restrict__ col,
                                         const int64_t* __restrict__ off,
                                         int64_t n_tgt, int64_t feat,
+                                        const float* __restrict__ amax_parts,
+    int n_parts,
                                         float* __restrict__ dx) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t wave =
       (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
   const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
   const int64_t ostride = 2 * feat;
+  const float magic = grid_magic(amax_parts, n_parts);
   for (int64_t t = wave; t < n_tgt; t += n_waves) {
     const int64_t s = off[t], e = off[t + 1];
     for (int64_t f = lane; f < feat; f += kWave)
       atomicAdd(&dx[t * feat + f],
-                static_cast<float>(dy[t * ostride + feat + f]));
+                snap(static_cast<float>(dy[t * ostride + feat + f]), magic));
     if (e <= s) continue;
     const float inv = 1.0f / (float)(e - s);
     for (int64_t k = s; k < e; ++k) {
       const int64_t c = col[k];
       for (int64_t f = lane; f < feat; f += kWave)
         atomicAdd(&dx[c * feat + f],
-                  static_cast<float>(dy[t * ostride + f]) * inv);
+                  snap(static_cast<float>(dy[t * ostride + f]) * inv, magic));
     }
   }
 }
@@ -379,24 +460,60 @@ torch::Tensor hip_segment_mean_cat_fwd(const torch::Tensor& x,
   return out;
 }
 
+// fp32 accumulation arena [n_src, feat]; in order-independent mode it is
+// followed by the block maxima of |dy|, and zero_absmax_kernel zeroes
+// the first and fills the second.
+struct BwdArena {
+  torch::Tensor dx;
+  float* parts;
+  int n_parts;
+};
+
+template <typename scalar_t>
+BwdArena make_bwd_arena(const torch::Tensor& dyc, int64_t n_src,
+                        int64_t feat, bool order_independent) {
+  if (!order_independent)  // plain mode: zero fill, no grid (n_parts == 0)
+    return {torch::zeros({n_src, feat},
+                         dyc.options().dtype(torch::kFloat32)),
+            nullptr, 0};
+  const int64_t n_arena = n_src * feat, n = dyc.numel();
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(
+      (std::max(n_arena / 4, n) + kZeroBlock - 1) / kZeroBlock,
+      kMaxAmaxParts));
+  auto flat = torch::empty({n_arena + blocks},
+                           dyc.options().dtype(torch::kFloat32));
+  float* base = flat.data_ptr<float>();
+  hipLaunchKernelGGL(zero_absmax_kernel<scalar_t>, dim3(blocks),
+                     dim3(kZeroBlock), 0, current_stream(), base, n_arena,
+                     dyc.data_ptr<scalar_t>(), n, base + n_arena);
+  return {flat.narrow(0, 0, n_arena).view({n_src, feat}), base + n_arena,
+          blocks};
+}
+
 // Returns fp32 regardless of dy dtype (fp32 atomic accumulation arena);
 // the python wrapper casts to dy.dtype once.
 torch::Tensor hip_segment_mean_cat_bwd(const torch::Tensor& dy,
                                        const torch::Tensor& col,
                                        const torch::Tensor& offsets,
-                                       int64_t n_src) {
+                                       int64_t n_src,
+                                       bool order_independent) {
   const int64_t n_tgt = dy.size(0);
   const int64_t feat = dy.size(1) / 2;
-  auto dx = torch::zeros({n_src, feat}, dy.options().dtype(torch::kFloat32));
-  if (n_tgt > 0) {
+  torch::Tensor dx;
+  if (n_tgt == 0)
+    return torch::zeros({n_src, feat}, dy.options().dtype(torch::kFloat32));
+  {
     auto dyc = dy.contiguous();
     GLT_DISPATCH_SEG(dy.scalar_type(), "segment_mean_cat_bwd", [&] {
+      auto arena = make_bwd_arena<scalar_t>(dyc, n_src, feat,
+                                            order_independent);
+      dx = arena.dx;
       hipLaunchKernelGGL(seg_mean_cat_bwd_kernel<scalar_t>,
                          dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
                          current_stream(), dyc.data_ptr<scalar_t>(),
                          col.data_ptr<int64_t>(),
                          offsets.data_ptr<int64_t>(), n_tgt, feat,
-                         dx.data_ptr<float>());
+                         arena.parts, arena.n_parts, dx.data_ptr<float>());
     });
   }
   return dx;
@@ -405,19 +522,24 @@ torch::Tensor hip_segment_mean_cat_bwd(const torch::Tensor& dy,
 torch::Tensor hip_segment_mean_bwd(const torch::Tensor& dy,
                                    const torch::Tensor& col,
                                    const torch::Tensor& offsets,
-                                   int64_t n_src) {
+                                   int64_t n_src, bool order_independent) {
   const int64_t n_tgt = dy.size(0);
   const int64_t feat = dy.size(1);
-  auto dx = torch::zeros({n_src, feat}, dy.options().dtype(torch::kFloat32));
-  if (n_tgt > 0) {
+  torch::Tensor dx;
+  if (n_tgt == 0)
+    return torch::zeros({n_src, feat}, dy.options().dtype(torch::kFloat32));
+  {
     auto dyc = dy.contiguous();
     GLT_DISPATCH_SEG(dy.scalar_type(), "segment_mean_bwd", [&] {
+      auto arena = make_bwd_arena<scalar_t>(dyc, n_src, feat,
+                                            order_independent);
+      dx = arena.dx;
       hipLaunchKernelGGL(seg_mean_bwd_kernel<scalar_t>,
                          dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
                          current_stream(), dyc.data_ptr<scalar_t>(),
                          col.data_ptr<int64_t>(),
                          offsets.data_ptr<int64_t>(), n_tgt, feat,
-                         dx.data_ptr<float>());
+                         arena.parts, arena.n_parts, dx.data_ptr<float>());
     });
   }
   return dx;

@@ -105,7 +105,8 @@ torch::Tensor hip_segment_mean_fwd(const torch::Tensor& x,
 torch::Tensor hip_segment_mean_bwd(const torch::Tensor& dy,
                                    const torch::Tensor& col,
                                    const torch::Tensor& offsets,
-                                   int64_t n_src);
+                                   int64_t n_src,
+                                   bool order_independent = false);
 // Fused [mean-agg | x-prefix] assembly (skips the dim-1 torch.cat).
 torch::Tensor hip_segment_mean_cat_fwd(const torch::Tensor& x,
                                        const torch::Tensor& col,
@@ -114,7 +115,8 @@ torch::Tensor hip_segment_mean_cat_fwd(const torch::Tensor& x,
 torch::Tensor hip_segment_mean_cat_bwd(const torch::Tensor& dy,
                                        const torch::Tensor& col,
                                        const torch::Tensor& offsets,
-                                       int64_t n_src);
+                                       int64_t n_src,
+                                       bool order_independent = false);
 
 // --- fused GAT edge softmax + aggregation (hip_gat.hip) ---------------------
 // Attention logits are computed inside the kernels from (h, att) directly.

@@ -141,11 +141,15 @@ class DistNeighborSampler:
 
     def _schedule(self, coro):
         if self.channel is not None:
-            def push(fut):
-                msg = fut.result()
-                self.channel.send(msg)
+            # send inside the task, not from a done-callback: a waiter on
+            # the returned future wakes BEFORE done-callbacks run, so a
+            # producer that waits on its futures and then sends '#END'
+            # could overtake the last batch (the trainer then ends the
+            # epoch one batch short and drops the late message)
+            async def produce_and_send():
+                self.channel.send(await coro)
 
-            return self.event_loop.add_task(coro, callback=push)
+            return self.event_loop.add_task(produce_and_send())
         return self.event_loop.add_task(coro)
 
     # ------------------------------------------------------------------

@@ -7,6 +7,26 @@ index_add on CPU or unsorted input.
 import torch
 
 _boundary_cache = {}
+_deterministic = False
+
+
+def set_deterministic(on: bool) -> None:
+    """Run-to-run reproducible segment backward (off by default).
+
+    The default backward adds fp32 atomics in whatever order they land,
+    so low-order bits differ between runs.  Deterministic mode snaps each
+    term to a power-of-two grid below max|dY| so the sums are exact in
+    any order (see csrc/hip/hip_segment.hip for the headroom condition).
+    It costs precision for terms far below max|dY|: up to 2^-18 max|dY|
+    absolute per term.  Also on while
+    ``torch.are_deterministic_algorithms_enabled()``.
+    """
+    global _deterministic
+    _deterministic = bool(on)
+
+
+def is_deterministic() -> bool:
+    return _deterministic or torch.are_deterministic_algorithms_enabled()
 
 
 def _boundaries(n: int, device) -> torch.Tensor:
@@ -36,7 +56,8 @@ class _SegmentMean(torch.autograd.Function):
 
         col, offsets = ctx.saved_tensors
         # kernel accumulates in an fp32 arena regardless of dy dtype
-        dx = _C.segment_mean_bwd(dy.contiguous(), col, offsets, ctx.n_src)
+        dx = _C.segment_mean_bwd(dy.contiguous(), col, offsets, ctx.n_src,
+                                 is_deterministic())
         if dx.dtype != dy.dtype:
             dx = dx.to(dy.dtype)
         return dx, None, None, None
@@ -62,7 +83,7 @@ class _SegmentMeanCat(torch.autograd.Function):
 
         col, offsets = ctx.saved_tensors
         dx = _C.segment_mean_cat_bwd(dy.contiguous(), col, offsets,
-                                     ctx.n_src)
+                                     ctx.n_src, is_deterministic())
         if dx.dtype != dy.dtype:
             dx = dx.to(dy.dtype)
         return dx, None, None, None
