@@ -266,6 +266,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("segment_mean_cat_bwd", &hip_segment_mean_cat_bwd, py::arg("dy"),
         py::arg("col"), py::arg("offsets"), py::arg("n_src"),
         py::arg("order_independent") = false);
+  m.def("segment_wsum_fwd", &hip_segment_wsum_fwd, py::arg("x"),
+        py::arg("col"), py::arg("offsets"), py::arg("w") = py::none(),
+        py::arg("a") = py::none(), py::arg("b") = py::none());
+  m.def("segment_wsum_bwd", &hip_segment_wsum_bwd, py::arg("dy"),
+        py::arg("x"), py::arg("col"), py::arg("offsets"), py::arg("w"),
+        py::arg("a"), py::arg("b"), py::arg("n_src"), py::arg("need_dx"),
+        py::arg("need_dw"), py::arg("order_independent") = false,
+        py::arg("coef_bound") = py::none());
 
   // Memory plumbing
   m.def("host_mapped_view", &host_mapped_view, py::arg("src"),

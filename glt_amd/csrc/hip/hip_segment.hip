@@ -27,6 +27,10 @@
  * traffic.  Backward always accumulates into an fp32 arena (bf16 atomics
  * lose too much precision for degree-weighted sums); the python wrapper
  * casts once at the end.
+ *
+ * seg_wsum_*: the weighted segment sum behind GCNConv and edge weights
+ * (out[t] = a[t] * sum_e w[e] * b[col[e]] * x[col[e]]) with its dx and
+ * per-edge dw backward; same layout, arena and order-independent mode.
  */
 #include <hip/hip_bf16.h>
 
@@ -233,14 +237,19 @@ zero_absmax_kernel(float* __restrict__ arena, int64_t n_arena,
 // |v| <= max|dY| < 2^e to a multiple of ulp(M) = q.  0 = do not snap
 // (n_parts == 0: plain mode; empty / non-finite dY; q outside the normal
 // range).  Wave-uniform: every lane folds the same n_parts <=
-// kMaxAmaxParts block maxima.
+// kMaxAmaxParts block maxima.  scale (optional, one device float) is a
+// bound on the factor each dY value is multiplied by before it is
+// snapped: the grid then sits below max|dY| * scale, the largest term.
 __device__ __forceinline__ float grid_magic(const float* __restrict__ parts,
-                                            int n_parts) {
+                                            int n_parts,
+                                            const float* __restrict__ scale =
+                                                nullptr) {
   float a = 0.f;
   for (int i = threadIdx.x & (kWave - 1); i < n_parts; i += kWave)
     a = fmaxf(a, parts[i]);
   for (int o = kWave / 2; o > 0; o >>= 1)
     a = fmaxf(a, __shfl_xor(a, o, kWave));
+  if (scale != nullptr) a *= fabsf(*scale);
   if (!(a > 0.f) || !isfinite(a)) return 0.f;
   int e;
   frexpf(a, &e);
@@ -364,6 +373,246 @@ __global__ void seg_mean_cat_bwd_kernel(const scalar_t* __restrict__ dy,
       for (int64_t f = lane; f < feat; f += kWave)
         atomicAdd(&dx[c * feat + f],
                   snap(static_cast<float>(dy[t * ostride + f]) * inv, magic));
+    }
+  }
+}
+
+// The wave index is the same in all 64 lanes, but derived from
+// threadIdx the compiler cannot see it: passing it through readfirstlane
+// lets everything indexed by the target or the edge (offsets, col, and
+// the w / a / b factors) use the scalar unit, one load per wave.
+__device__ __forceinline__ int64_t wave_uniform(int64_t v) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+  const uint32_t hi =
+      __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// ---------------------------------------------------------------------------
+// Weighted segment sum (GCN-style aggregation):
+//   out[t, :] = a[t] * sum_{e in [off[t], off[t+1])} w[e] * b[col[e]] * x[col[e], :]
+// w (per edge), a (per target) and b (per source) are optional fp32
+// factors; a null pointer means 1.  The per-edge coefficient w[e] * b[c]
+// has a wave-uniform address, so it is loaded once per edge and not once
+// per lane-channel.  Same wave-per-target layout as seg_mean_fwd_kernel.
+// ---------------------------------------------------------------------------
+
+// Row addresses and factors of up to 8 edges starting at k0, all in
+// scalar registers.  Slots past the end of the segment repeat edge k0 (a
+// valid row) so the loads that follow need no branch; the caller drops
+// their products.  A null w or b means 1.
+__device__ __forceinline__ void wsum_edge_batch(
+    const int64_t* __restrict__ col, const float* __restrict__ w,
+    const float* __restrict__ b, int64_t k0, int nb, int64_t stride,
+    int64_t (&cc)[8], float (&cw)[8], float (&cb)[8]) {
+  int64_t c[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) c[q] = col[q < nb ? k0 + q : k0];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    cc[q] = c[q] * stride;
+    cw[q] = 1.0f;
+    cb[q] = 1.0f;
+  }
+  if (w != nullptr) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) cw[q] = w[q < nb ? k0 + q : k0];
+  }
+  if (b != nullptr) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) cb[q] = b[c[q]];
+  }
+}
+
+template <typename scalar_t, bool kW, bool kB>
+__global__ void seg_wsum_fwd_kernel(const scalar_t* __restrict__ x,
+                                    const int64_t* __restrict__ col,
+                                    const int64_t* __restrict__ off,
+                                    const float* __restrict__ w,
+                                    const float* __restrict__ a,
+                                    const float* __restrict__ b,
+                                    int64_t n_tgt, int64_t feat,
+                                    scalar_t* __restrict__ out) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = wave_uniform(
+      (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave);
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  for (int64_t t = wave; t < n_tgt; t += n_waves) {
+    const int64_t s = off[t], e = off[t + 1];
+    const float at = a != nullptr ? a[t] : 1.0f;
+    // 128 channels per pass (lane owns f and f+64), register accumulators,
+    // 8 edges per batch: 16 independent row loads in flight per lane.
+    // Lanes past the row end read its last channel and do not store.
+    for (int64_t fb = 0; fb < feat; fb += 2 * kWave) {
+      const int64_t f0 = fb + lane, f1 = fb + lane + kWave;
+      const int64_t g0 = f0 < feat ? f0 : feat - 1;
+      const int64_t g1 = f1 < feat ? f1 : feat - 1;
+      const bool two = fb + kWave < feat;  // wave-uniform
+      float a0 = 0.f, a1 = 0.f;
+      for (int64_t k0 = s; k0 < e; k0 += 8) {
+        const int nb = (int)((e - k0) < 8 ? (e - k0) : 8);
+        int64_t cc[8];
+        float cw[8], cf[8], v0[8], v1[8];
+        wsum_edge_batch(col, kW ? w : nullptr, kB ? b : nullptr, k0, nb,
+                        feat, cc, cw, cf);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) cf[q] *= cw[q];
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+          v0[q] = static_cast<float>(x[cc[q] + g0]);
+        if (two) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q)
+            v1[q] = static_cast<float>(x[cc[q] + g1]);
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) a0 += q < nb ? cf[q] * v0[q] : 0.f;
+        if (two) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q) a1 += q < nb ? cf[q] * v1[q] : 0.f;
+        }
+      }
+      if (f0 < feat) out[t * feat + f0] = static_cast<scalar_t>(a0 * at);
+      if (f1 < feat) out[t * feat + f1] = static_cast<scalar_t>(a1 * at);
+    }
+  }
+}
+
+// bf16 fast path for even F: each lane owns two adjacent channels (one
+// 4-byte load per row visit), 64 pairs per pass.
+template <bool kW, bool kB>
+__global__ void seg_wsum_fwd_bf162_kernel(
+    const __hip_bfloat162* __restrict__ x, const int64_t* __restrict__ col,
+    const int64_t* __restrict__ off, const float* __restrict__ w,
+    const float* __restrict__ a, const float* __restrict__ b, int64_t n_tgt,
+    int64_t feat2, __hip_bfloat162* __restrict__ out) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = wave_uniform(
+      (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave);
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  for (int64_t t = wave; t < n_tgt; t += n_waves) {
+    const int64_t s = off[t], e = off[t + 1];
+    const float at = a != nullptr ? a[t] : 1.0f;
+    for (int64_t fb = 0; fb < feat2; fb += kWave) {
+      const int64_t f = fb + lane;
+      const int64_t g = f < feat2 ? f : feat2 - 1;
+      float2 acc = {0.f, 0.f};
+      for (int64_t k0 = s; k0 < e; k0 += 8) {
+        const int nb = (int)((e - k0) < 8 ? (e - k0) : 8);
+        int64_t cc[8];
+        float cw[8], cf[8];
+        __hip_bfloat162 v[8];
+        wsum_edge_batch(col, kW ? w : nullptr, kB ? b : nullptr, k0, nb,
+                        feat2, cc, cw, cf);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) cf[q] *= cw[q];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = x[cc[q] + g];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const float2 u = __bfloat1622float2(v[q]);
+          acc.x += q < nb ? cf[q] * u.x : 0.f;
+          acc.y += q < nb ? cf[q] * u.y : 0.f;
+        }
+      }
+      if (f < feat2)
+        out[t * feat2 + f] =
+            __float22bfloat162_rn({acc.x * at, acc.y * at});
+    }
+  }
+}
+
+// Backward of the weighted segment sum, for every edge e = (t, c):
+//   kDx: dx[c, :] += a[t] * w[e] * b[c] * dy[t, :]   (fp32 atomics, arena)
+//   kDw: dw[e]     = a[t] * b[c] * <dy[t, :], x[c, :]>
+// dw is a per-edge wave dot product (xor-shuffle reduction) written with
+// one plain store per edge: no atomics, so it is the same bits every run.
+// Without kDw x is never read.  In order-independent mode the terms are
+// bounded by max|dy| * coef_bound (coef_bound >= max|a| max|w| max|b|), so
+// the grid exponent comes from that product.
+template <typename scalar_t, bool kDx, bool kDw>
+__global__ void seg_wsum_bwd_kernel(const scalar_t* __restrict__ dy,
+                                    const scalar_t* __restrict__ x,
+                                    const int64_t* __restrict__ col,
+                                    const int64_t* __restrict__ off,
+                                    const float* __restrict__ w,
+                                    const float* __restrict__ a,
+                                    const float* __restrict__ b,
+                                    int64_t n_tgt, int64_t feat,
+                                    const float* __restrict__ amax_parts,
+                                    int n_parts,
+                                    const float* __restrict__ coef_bound,
+                                    float* __restrict__ dx,
+                                    float* __restrict__ dw) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = wave_uniform(
+      (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave);
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const float magic =
+      kDx ? grid_magic(amax_parts, n_parts, coef_bound) : 0.f;
+  const bool in_regs = feat <= 2 * kWave;
+  const bool two = feat > kWave;
+  const int64_t f0 = lane, f1 = lane + kWave;
+  // clamped channels: x loads for dw are issued for all 64 lanes
+  const int64_t c0 = f0 < feat ? f0 : feat - 1;
+  const int64_t c1 = f1 < feat ? f1 : feat - 1;
+  for (int64_t t = wave; t < n_tgt; t += n_waves) {
+    const int64_t s = off[t], e = off[t + 1];
+    if (e <= s) continue;
+    const float at = a != nullptr ? a[t] : 1.0f;
+    // the dy row is shared by every edge of the segment
+    float g0 = 0.f, g1 = 0.f;
+    if (in_regs) {
+      if (f0 < feat) g0 = static_cast<float>(dy[t * feat + f0]);
+      if (f1 < feat) g1 = static_cast<float>(dy[t * feat + f1]);
+    }
+    for (int64_t k0 = s; k0 < e; k0 += 8) {
+      const int nb = (int)((e - k0) < 8 ? (e - k0) : 8);
+      int64_t cc[8];
+      float cw[8], cb[8];
+      wsum_edge_batch(col, w, b, k0, nb, feat, cc, cw, cb);
+      float x0[8], x1[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) x0[q] = x1[q] = 0.f;
+      if (kDw && in_regs) {  // 8 (16) independent row loads in flight
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+          x0[q] = static_cast<float>(x[cc[q] + c0]);
+        if (two) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q)
+            x1[q] = static_cast<float>(x[cc[q] + c1]);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        if (q < nb) {  // wave-uniform
+          const float ab = at * cb[q];
+          const float coef = ab * cw[q];
+          float dot = 0.f;
+          if (in_regs) {
+            if (f0 < feat) {
+              if (kDx) atomicAdd(&dx[cc[q] + f0], snap(g0 * coef, magic));
+              if (kDw) dot += g0 * x0[q];
+            }
+            if (f1 < feat) {
+              if (kDx) atomicAdd(&dx[cc[q] + f1], snap(g1 * coef, magic));
+              if (kDw) dot += g1 * x1[q];
+            }
+          } else {
+            for (int64_t f = lane; f < feat; f += kWave) {
+              const float g = static_cast<float>(dy[t * feat + f]);
+              if (kDx) atomicAdd(&dx[cc[q] + f], snap(g * coef, magic));
+              if (kDw) dot += g * static_cast<float>(x[cc[q] + f]);
+            }
+          }
+          if (kDw) {
+            for (int o = kWave / 2; o > 0; o >>= 1)
+              dot += __shfl_xor(dot, o, kWave);
+            if (lane == 0) dw[k0 + q] = ab * dot;
+          }
+        }
+      }
     }
   }
 }
@@ -544,5 +793,164 @@ torch::Tensor hip_segment_mean_bwd(const torch::Tensor& dy,
   }
   return dx;
 }
+
+namespace {
+
+// optional fp32 factor of the weighted segment sum -> device pointer
+const float* wsum_factor(const c10::optional<torch::Tensor>& t, int64_t n,
+                         const char* what) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                  t->scalar_type() == torch::kFloat32 && t->numel() == n,
+              "segment_wsum: ", what, " must be contiguous fp32 on device "
+              "with ", n, " elements");
+  return t->data_ptr<float>();
+}
+
+void wsum_check_index(const torch::Tensor& col, const torch::Tensor& offsets,
+                      int64_t n_tgt) {
+  TORCH_CHECK(col.is_cuda() && col.is_contiguous() &&
+                  col.scalar_type() == torch::kInt64 && offsets.is_cuda() &&
+                  offsets.is_contiguous() &&
+                  offsets.scalar_type() == torch::kInt64,
+              "segment_wsum: col/offsets must be contiguous int64 on device");
+  TORCH_CHECK(offsets.numel() == n_tgt + 1,
+              "segment_wsum: offsets must have n_tgt + 1 entries");
+}
+
+}  // namespace
+
+// absent edge weight / source scale -> compile-time flags (no ones tensor,
+// no per-edge branch)
+#define GLT_WSUM_FLAGS(HAS_W, HAS_B, ...)                 \
+  [&] {                                                   \
+    if (HAS_W) {                                          \
+      constexpr bool kW = true;                           \
+      if (HAS_B) {                                        \
+        constexpr bool kB = true;                         \
+        return __VA_ARGS__();                             \
+      }                                                   \
+      constexpr bool kB = false;                          \
+      return __VA_ARGS__();                               \
+    }                                                     \
+    constexpr bool kW = false;                            \
+    if (HAS_B) {                                          \
+      constexpr bool kB = true;                           \
+      return __VA_ARGS__();                               \
+    }                                                     \
+    constexpr bool kB = false;                            \
+    return __VA_ARGS__();                                 \
+  }()
+
+torch::Tensor hip_segment_wsum_fwd(const torch::Tensor& x,
+                                   const torch::Tensor& col,
+                                   const torch::Tensor& offsets,
+                                   const c10::optional<torch::Tensor>& w,
+                                   const c10::optional<torch::Tensor>& a,
+                                   const c10::optional<torch::Tensor>& b) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2,
+              "segment_wsum: x must be a contiguous [n_src, F] device tensor");
+  const int64_t n_tgt = offsets.numel() - 1;
+  const int64_t feat = x.size(1);
+  wsum_check_index(col, offsets, n_tgt);
+  const float* wp = wsum_factor(w, col.numel(), "edge weight");
+  const float* ap = wsum_factor(a, n_tgt, "target scale");
+  const float* bp = wsum_factor(b, x.size(0), "source scale");
+  auto out = torch::empty({n_tgt, feat}, x.options());
+  if (n_tgt > 0 && feat > 0) {
+    const bool hw = wp != nullptr, hb = bp != nullptr;
+    if (x.scalar_type() == torch::kBFloat16 && feat % 2 == 0) {
+      auto x2 = reinterpret_cast<const __hip_bfloat162*>(x.data_ptr());
+      auto o2 = reinterpret_cast<__hip_bfloat162*>(out.data_ptr());
+      GLT_WSUM_FLAGS(hw, hb, [&] {
+        hipLaunchKernelGGL((seg_wsum_fwd_bf162_kernel<kW, kB>),
+                           dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
+                           current_stream(), x2, col.data_ptr<int64_t>(),
+                           offsets.data_ptr<int64_t>(), wp, ap, bp, n_tgt,
+                           feat / 2, o2);
+      });
+      return out;
+    }
+    GLT_DISPATCH_SEG(x.scalar_type(), "segment_wsum_fwd", [&] {
+      GLT_WSUM_FLAGS(hw, hb, [&] {
+        hipLaunchKernelGGL((seg_wsum_fwd_kernel<scalar_t, kW, kB>),
+                           dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
+                           current_stream(), x.data_ptr<scalar_t>(),
+                           col.data_ptr<int64_t>(),
+                           offsets.data_ptr<int64_t>(), wp, ap, bp, n_tgt,
+                           feat, out.data_ptr<scalar_t>());
+      });
+    });
+  }
+  return out;
+}
+
+#define GLT_WSUM_BWD(DX, DW)                                              \
+  hipLaunchKernelGGL((seg_wsum_bwd_kernel<scalar_t, DX, DW>),             \
+                     dim3(wave_grid(n_tgt)), dim3(kBlock), 0,             \
+                     current_stream(), dyc.data_ptr<scalar_t>(), xp,      \
+                     col.data_ptr<int64_t>(),                             \
+                     offsets.data_ptr<int64_t>(), wp, ap, bp, n_tgt,      \
+                     feat, arena.parts, arena.n_parts, cbp, dxp, dwp)
+
+// (dx, dw): dx is fp32 [n_src, F] (accumulation arena; the python wrapper
+// casts once), dw is fp32 [E]; each is None unless asked for.  x is only
+// needed (and only read) for dw.
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+hip_segment_wsum_bwd(const torch::Tensor& dy,
+                     const c10::optional<torch::Tensor>& x,
+                     const torch::Tensor& col, const torch::Tensor& offsets,
+                     const c10::optional<torch::Tensor>& w,
+                     const c10::optional<torch::Tensor>& a,
+                     const c10::optional<torch::Tensor>& b, int64_t n_src,
+                     bool need_dx, bool need_dw, bool order_independent,
+                     const c10::optional<torch::Tensor>& coef_bound) {
+  TORCH_CHECK(dy.is_cuda() && dy.dim() == 2,
+              "segment_wsum_bwd: dy must be a [n_tgt, F] device tensor");
+  const int64_t n_tgt = dy.size(0);
+  const int64_t feat = dy.size(1);
+  const int64_t n_edge = col.numel();
+  wsum_check_index(col, offsets, n_tgt);
+  const float* wp = wsum_factor(w, n_edge, "edge weight");
+  const float* ap = wsum_factor(a, n_tgt, "target scale");
+  const float* bp = wsum_factor(b, n_src, "source scale");
+  const float* cbp = order_independent && need_dx
+                         ? wsum_factor(coef_bound, 1, "coefficient bound")
+                         : nullptr;
+  if (need_dw)
+    TORCH_CHECK(x.has_value() && x->is_cuda() && x->is_contiguous() &&
+                    x->dim() == 2 && x->size(0) == n_src &&
+                    x->size(1) == feat &&
+                    x->scalar_type() == dy.scalar_type(),
+                "segment_wsum_bwd: dw needs x as a contiguous [n_src, F] "
+                "tensor of dy's dtype");
+  const auto f32 = dy.options().dtype(torch::kFloat32);
+  c10::optional<torch::Tensor> dx, dw;
+  // zeros: edges past off[n_tgt] (targets >= n_tgt) get no gradient
+  if (need_dw) dw = torch::zeros({n_edge}, f32);
+  if (n_tgt == 0 || feat == 0 || n_edge == 0 || !(need_dx || need_dw)) {
+    if (need_dx) dx = torch::zeros({n_src, feat}, f32);
+    return {dx, dw};
+  }
+  auto dyc = dy.contiguous();
+  GLT_DISPATCH_SEG(dy.scalar_type(), "segment_wsum_bwd", [&] {
+    BwdArena arena{torch::Tensor(), nullptr, 0};
+    if (need_dx) {
+      arena = make_bwd_arena<scalar_t>(dyc, n_src, feat, order_independent);
+      dx = arena.dx;
+    }
+    const scalar_t* xp = need_dw ? x->data_ptr<scalar_t>() : nullptr;
+    float* dxp = need_dx ? arena.dx.data_ptr<float>() : nullptr;
+    float* dwp = need_dw ? dw->data_ptr<float>() : nullptr;
+    if (need_dx && need_dw)
+      GLT_WSUM_BWD(true, true);
+    else if (need_dx)
+      GLT_WSUM_BWD(true, false);
+    else
+      GLT_WSUM_BWD(false, true);
+  });
+  return {dx, dw};
+}
+#undef GLT_WSUM_BWD
 
 }  // namespace glt

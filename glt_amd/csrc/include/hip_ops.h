@@ -118,6 +118,26 @@ torch::Tensor hip_segment_mean_cat_bwd(const torch::Tensor& dy,
                                        int64_t n_src,
                                        bool order_independent = false);
 
+// Weighted segment sum: out[t] = a[t] * sum_e w[e] * b[col[e]] * x[col[e]]
+// with optional fp32 factors (absent = 1).  bwd returns (dx fp32, dw fp32),
+// each None unless requested; x is only read for dw.  coef_bound: 0-dim
+// fp32 device bound on |a| |w| |b|, used in order-independent mode.
+torch::Tensor hip_segment_wsum_fwd(const torch::Tensor& x,
+                                   const torch::Tensor& col,
+                                   const torch::Tensor& offsets,
+                                   const c10::optional<torch::Tensor>& w,
+                                   const c10::optional<torch::Tensor>& a,
+                                   const c10::optional<torch::Tensor>& b);
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+hip_segment_wsum_bwd(const torch::Tensor& dy,
+                     const c10::optional<torch::Tensor>& x,
+                     const torch::Tensor& col, const torch::Tensor& offsets,
+                     const c10::optional<torch::Tensor>& w,
+                     const c10::optional<torch::Tensor>& a,
+                     const c10::optional<torch::Tensor>& b, int64_t n_src,
+                     bool need_dx, bool need_dw, bool order_independent,
+                     const c10::optional<torch::Tensor>& coef_bound);
+
 // --- fused GAT edge softmax + aggregation (hip_gat.hip) ---------------------
 // Attention logits are computed inside the kernels from (h, att) directly.
 // fwd returns (out, m, Z, s_pre); bwd consumes the cached s_pre logits.

@@ -8,8 +8,9 @@ source/neighbor local index; aggregation flows 1 -> 0.
 
 Dense math lands on hipBLASLt through torch.nn.Linear (or the in-house
 MFMA GEMM for skinny shapes); sparse aggregation uses the fused HIP
-kernels in csrc/hip/ (segment-mean [+root concat], GAT edge-softmax) on
-GPU fp32 batches, with an index_add_ fallback for CPU/other dtypes.
+kernels in csrc/hip/ (segment-mean [+root concat], weighted segment sum,
+GAT edge-softmax) on GPU fp32/bf16 batches, with an index_add_ fallback
+for CPU/other dtypes.
 """
 
 import torch
@@ -109,22 +110,40 @@ class GCNConv(nn.Module):
         super().__init__()
         self.lin = nn.Linear(in_channels, out_channels, bias=bias)
 
-    def forward(self, x, edge_index, num_target: int = None):
+    def forward(self, x, edge_index, num_target: int = None,
+                edge_weight: torch.Tensor = None,
+                sorted_by_target: bool = False):
+        """edge_weight: optional non-negative [E] per-edge weight; the
+        degree of a node is then the sum of the weights of its edges
+        (either end), nodes of degree 0 get norm 0, and the normalisation
+        is a constant (no gradient flows to edge_weight through it).
+        sorted_by_target: set True for edges sorted by edge_index[0]
+        (loader batches) to run the fused HIP aggregation on the GPU."""
+        from .. import ops
+        from ..ops.segment import _wsum_fused
+
         n = x.size(0)
         nt = num_target if num_target is not None else n
         tgt, src = edge_index[0], edge_index[1]
-        deg = _degree(torch.cat([tgt, src]), n).to(x.dtype)
-        norm = deg.rsqrt()
+        # the kernels take fp32 factors; the torch path keeps x's dtype
+        ndt = torch.float32 if _wsum_fused(x, sorted_by_target) else x.dtype
+        if edge_weight is None:
+            deg = _degree(torch.cat([tgt, src]), n).to(ndt)
+            norm = deg.rsqrt()
+        else:
+            w = edge_weight.detach().to(
+                torch.promote_types(x.dtype, torch.float32))
+            deg = w.new_zeros(n)
+            deg.index_add_(0, tgt, w)
+            deg.index_add_(0, src, w)
+            norm = torch.where(deg > 0, deg.rsqrt(),
+                               torch.zeros_like(deg)).to(ndt)
         if x.dtype != self.lin.weight.dtype:
-            from ..ops import cast_linear
-
-            h = cast_linear(x, self.lin.weight, self.lin.bias)
+            h = ops.cast_linear(x, self.lin.weight, self.lin.bias)
         else:
             h = self.lin(x)
-        msg = h.index_select(0, src) * norm[src].unsqueeze(1)
-        out = h.new_zeros(nt, h.size(1))
-        out.index_add_(0, tgt, msg)
-        return out * norm[:nt].unsqueeze(1)
+        return ops.segment_weighted_sum(h, tgt, src, nt, edge_weight,
+                                        norm[:nt], norm, sorted_by_target)
 
 
 class GATConv(nn.Module):

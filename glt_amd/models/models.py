@@ -107,16 +107,28 @@ class GCN(nn.Module):
         self.dropout = dropout
 
     def forward(self, x, edge_index, num_sampled_nodes=None,
-                num_sampled_edges=None):
+                num_sampled_edges=None, edge_weight=None,
+                sorted_by_target=None):
+        """edge_weight: optional non-negative [E] weights aligned with
+        edge_index (e.g. ``data.edge_attr[:, 0]`` of a ``with_edge=True``
+        loader).  sorted_by_target=None picks the fused aggregation
+        exactly when trim lists are given: those only come from the
+        loaders, whose batches are target-ascending across hops; a GCN
+        called on arbitrary edges keeps the order-agnostic path."""
         L = len(self.convs)
         for i, conv in enumerate(self.convs):
             trim = _layer_trim(num_sampled_nodes, num_sampled_edges, L, i)
             if trim is not None:
                 n_in, n_edges, n_out = trim
                 x = conv(x[:n_in], edge_index[:, :n_edges],
-                         num_target=n_out)
+                         num_target=n_out,
+                         edge_weight=None if edge_weight is None
+                         else edge_weight[:n_edges],
+                         sorted_by_target=True if sorted_by_target is None
+                         else sorted_by_target)
             else:
-                x = conv(x, edge_index)
+                x = conv(x, edge_index, edge_weight=edge_weight,
+                         sorted_by_target=bool(sorted_by_target))
             if i < L - 1:
                 x = F.relu(x)
                 x = F.dropout(x, p=self.dropout, training=self.training)

@@ -1,8 +1,10 @@
-"""Autograd wrapper over the fused HIP segment-mean kernel.
+"""Autograd wrappers over the fused HIP segment kernels.
 
-Used by SAGEConv when the batch lives on the GPU and edges are sorted by
-target (the glt_amd sampler's native edge order); falls back to torch
-index_add on CPU or unsorted input.
+segment_mean / segment_mean_cat: used by SAGEConv when the batch lives on
+the GPU and edges are sorted by target (the glt_amd sampler's native edge
+order); the layer falls back to torch index_add on CPU or unsorted input.
+segment_weighted_sum: GCNConv's aggregation and the edge-weight
+primitive; picks the kernels or a torch composition itself.
 """
 import torch
 
@@ -108,3 +110,94 @@ def segment_mean_cat(x: torch.Tensor, tgt: torch.Tensor, src: torch.Tensor,
     offsets = torch.searchsorted(tgt, _boundaries(n_tgt, tgt.device))
     return _SegmentMeanCat.apply(x.contiguous(), src.contiguous(), offsets,
                                  n_tgt)
+
+
+class _SegmentWeightedSum(torch.autograd.Function):
+    """out[t] = a[t] * sum_e w[e] * b[col[e]] * x[col[e]] over the HIP
+    kernels; w, a, b are fp32 or None.  Gradients for x and w only."""
+
+    @staticmethod
+    def forward(ctx, x, w, col, offsets, a, b):
+        from .. import _C
+
+        need_dw = w is not None and ctx.needs_input_grad[1]
+        # x is kept (and later read) only for the edge-weight gradient
+        ctx.save_for_backward(col, offsets, w, a, b, x if need_dw else None)
+        ctx.n_src = x.size(0)
+        return _C.segment_wsum_fwd(x, col, offsets, w, a, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .. import _C
+
+        col, offsets, w, a, b, x = ctx.saved_tensors
+        need_dx = ctx.needs_input_grad[0]
+        need_dw = w is not None and ctx.needs_input_grad[1]
+        det = is_deterministic()
+        bound = None
+        if det and need_dx and col.numel() > 0 and dy.size(0) > 0:
+            # terms are bounded by max|dy| * max|a| * max|w| * max|b|
+            for f in (w, a, b):
+                if f is not None:
+                    m = f.abs().amax()
+                    bound = m if bound is None else bound * m
+        dx, dw = _C.segment_wsum_bwd(dy.contiguous(), x, col, offsets, w, a,
+                                     b, ctx.n_src, need_dx, need_dw, det,
+                                     bound)
+        # kernel accumulates in an fp32 arena regardless of dy dtype
+        if dx is not None and dx.dtype != dy.dtype:
+            dx = dx.to(dy.dtype)
+        return dx, dw, None, None, None, None
+
+
+def _wsum_fused(x: torch.Tensor, sorted_by_target: bool) -> bool:
+    """Whether segment_weighted_sum takes the HIP kernels for this input."""
+    return bool(sorted_by_target) and x.is_cuda and \
+        x.dtype in (torch.float32, torch.bfloat16)
+
+
+def segment_weighted_sum(x: torch.Tensor, tgt: torch.Tensor,
+                         src: torch.Tensor, n_tgt: int,
+                         edge_weight: torch.Tensor = None,
+                         tgt_scale: torch.Tensor = None,
+                         src_scale: torch.Tensor = None,
+                         sorted_by_target: bool = True) -> torch.Tensor:
+    """``out[t] = tgt_scale[t] * sum_{e: tgt[e]=t} edge_weight[e] *
+    src_scale[src[e]] * x[src[e]]``; returns [n_tgt, F].
+
+    edge_weight [E], tgt_scale [n_tgt] and src_scale [x.size(0)] are
+    optional (absent = 1) and may be any float dtype.  Gradients flow to x
+    and to edge_weight; the scales are constants and must not require
+    grad.  GPU fp32/bf16 input with ``sorted_by_target=True`` (tgt
+    ascending, the glt_amd batch order) runs the fused HIP kernels:
+    atomic-free forward with fp32 accumulation, fp32-arena backward that
+    follows ``is_deterministic()``, bit-reproducible edge-weight gradient.
+    Anything else runs a torch composition (index_select, mul,
+    index_add_).
+    """
+    for name, s in (("tgt_scale", tgt_scale), ("src_scale", src_scale)):
+        if s is not None and s.requires_grad:
+            raise ValueError(
+                f"segment_weighted_sum: {name} is not differentiable")
+    if _wsum_fused(x, sorted_by_target):
+        def f32(v):
+            return None if v is None else \
+                v.to(torch.float32).contiguous()
+
+        offsets = torch.searchsorted(tgt, _boundaries(n_tgt, tgt.device))
+        a = f32(tgt_scale)
+        if a is not None and a.numel() != n_tgt:
+            a = a[:n_tgt].contiguous()
+        return _SegmentWeightedSum.apply(x.contiguous(), f32(edge_weight),
+                                         src.contiguous(), offsets, a,
+                                         f32(src_scale))
+    msg = x.index_select(0, src)
+    if src_scale is not None:
+        msg = msg * src_scale.to(x.dtype)[src].unsqueeze(1)
+    if edge_weight is not None:
+        msg = msg * edge_weight.to(x.dtype).unsqueeze(1)
+    out = x.new_zeros(n_tgt, x.size(1))
+    out.index_add_(0, tgt, msg)
+    if tgt_scale is not None:
+        out = out * tgt_scale.to(x.dtype)[:n_tgt].unsqueeze(1)
+    return out

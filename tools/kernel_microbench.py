@@ -21,10 +21,20 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 
-def build_flagship_shapes(op, device):
+def build_flagship_shapes(op, device, bf16=False):
     """Layer-1-of-flagship shapes: ~590k rows, 890k edges, F=100/256."""
     torch.manual_seed(0)
     n_src, n_tgt, E, F = 590_000, 130_000, 890_000, 256
+    if op in ("seg_wsum", "seg_wsum_bf16", "gcn_conv",
+              "gcn_conv_composite"):
+        # F=256 fp32, or the bf16 feature-store shape F=100
+        if op == "seg_wsum_bf16" or bf16:
+            x = torch.randn(n_src, 100, device=device).to(torch.bfloat16)
+        else:
+            x = torch.randn(n_src, F, device=device)
+        tgt = torch.sort(torch.randint(0, n_tgt, (E,), device=device))[0]
+        src = torch.randint(0, n_src, (E,), device=device)
+        return (x, tgt, src, n_tgt)
     if op in ("seg_mean", "seg_mean_cat"):
         x = torch.randn(n_src, F, device=device)
         tgt = torch.sort(torch.randint(0, n_tgt, (E,), device=device))[0]
@@ -92,7 +102,12 @@ def main():
                              "mfma_gemm", "gather", "sample",
                              "sample_weighted", "sample_weighted_nr",
                              "sample_weighted_hub", "gemm_bt_bf16",
-                             "gemm_kt_bf16", "seg_mean_cat_bf16"])
+                             "gemm_kt_bf16", "seg_mean_cat_bf16",
+                             "seg_wsum", "seg_wsum_bf16", "gcn_conv",
+                             "gcn_conv_composite"])
+    ap.add_argument("--bf16", action="store_true",
+                    help="gcn_conv ops: bf16 input at F=100 (default fp32 "
+                         "at F=256)")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     args = ap.parse_args()
@@ -101,7 +116,7 @@ def main():
     import glt_amd
     from glt_amd import _C
 
-    inp = build_flagship_shapes(args.op, device)
+    inp = build_flagship_shapes(args.op, device, args.bf16)
 
     op = args.op
     if args.op == "seg_mean":
@@ -133,6 +148,28 @@ def main():
         x, tgt, src, n_tgt = inp
         off = torch.searchsorted(tgt, _boundaries(n_tgt, device))
         fn = lambda: _C.segment_mean_cat_fwd(x, src, off, n_tgt)
+    elif args.op in ("seg_wsum", "seg_wsum_bf16"):
+        # forward kernel with all three factors (the GCN aggregation)
+        from glt_amd.ops.segment import _boundaries
+        x, tgt, src, n_tgt = inp
+        off = torch.searchsorted(tgt, _boundaries(n_tgt, device))
+        w = torch.rand(src.numel(), device=device)
+        a = torch.rand(n_tgt, device=device)
+        b = torch.rand(x.size(0), device=device)
+        fn = lambda: _C.segment_wsum_fwd(x, src, off, w, a, b)
+    elif args.op in ("gcn_conv", "gcn_conv_composite"):
+        # GCNConv forward + backward (weight gradient only, as in layer
+        # 1): fused aggregation against the torch composition
+        from glt_amd.models.layers import GCNConv
+        x, tgt, src, n_tgt = inp
+        conv = GCNConv(x.size(1), 256).to(device)
+        ei = torch.stack([tgt, src])
+        fused = args.op == "gcn_conv"
+        gy = torch.randn(n_tgt, 256, device=device).to(x.dtype)
+
+        def fn():
+            conv.zero_grad(set_to_none=True)
+            conv(x, ei, n_tgt, sorted_by_target=fused).backward(gy)
     elif args.op == "gather":
         feats, rows = inp
         store = _C.UnifiedFeatureStore(0)
