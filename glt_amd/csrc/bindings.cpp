@@ -253,6 +253,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out_fp32") = false);
   m.def("gemm_kt_bf16", &hip_gemm_kt_bf16, py::arg("A"), py::arg("B"),
         py::arg("with_db") = false);
+  m.def(
+      "gemm_kt_bf16_plan",
+      [](int64_t Kb, int64_t M, int64_t N) {
+        const GemmKtPlan p = gemm_kt_bf16_plan(Kb, M, N);
+        return std::make_tuple(p.big, p.z, p.k_per_z);
+      },
+      py::arg("Kb"), py::arg("M"), py::arg("N"));
   m.def("mfma_bf16_selftest", &hip_mfma_bf16_selftest);
   m.def("gat_fused_fwd", &hip_gat_fused_fwd);
   m.def("gat_fused_bwd", &hip_gat_fused_bwd);

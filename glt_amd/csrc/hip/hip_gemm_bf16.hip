@@ -30,6 +30,7 @@
 
 #include "hip_common.h"
 #include "../include/common.h"
+#include "../include/hip_ops.h"
 
 namespace glt {
 
@@ -634,7 +635,7 @@ torch::Tensor hip_gemm_bt_bf16(const torch::Tensor& A,
   auto C = torch::empty({M, N}, A.options().dtype(
                                     out_fp32 ? torch::kFloat32
                                              : torch::kBFloat16));
-  if (M == 0) return C;
+  if (M == 0 || N == 0) return C;  // nothing to write, no zero-dim grid
   const float* bias_p = nullptr;
   torch::Tensor bias_f;
   if (bias.has_value()) {
@@ -676,6 +677,32 @@ torch::Tensor hip_gemm_bt_bf16(const torch::Tensor& A,
   return C;
 }
 
+// Tile size and split-K plan of hip_gemm_kt_bf16 (host arithmetic only;
+// the tests read it to assert which kernel and chunking a shape reaches).
+GemmKtPlan gemm_kt_bf16_plan(int64_t Kb, int64_t M, int64_t N) {
+  GemmKtPlan p;
+  // 128x128/8-wave tiles for big dW shapes (halves the A/B re-read
+  // amplification); 64x64 for small/tail-heavy outputs
+  p.big = (M >= KBM && N >= 96 && Kb >= 4096);
+  const int64_t bm = p.big ? KBM : GBM, bn = p.big ? KBN : GBN;
+  p.m_t = (M + bm - 1) / bm;
+  p.n_t = (N + bn - 1) / bn;
+  // split-K sized so the grid fills the 256 CUs a few times over
+  int64_t z = 1;
+  if (Kb > GBK) {
+    const int64_t want_wg = p.big ? 512 : 1024;
+    const int64_t tiles = std::max<int64_t>(1, p.m_t * p.n_t);
+    const int64_t want = (want_wg + tiles - 1) / tiles;
+    const int64_t max_z = (Kb + GBK - 1) / GBK;
+    z = std::max<int64_t>(1, std::min(want, max_z));
+  }
+  // at least one K step, so an empty Kb still plans one (empty) chunk
+  p.k_per_z =
+      std::max<int64_t>(GBK, ((Kb + z - 1) / z + GBK - 1) / GBK * GBK);
+  p.z = std::max<int64_t>(1, (Kb + p.k_per_z - 1) / p.k_per_z);
+  return p;
+}
+
 // (dW, db) = (A^T @ B, colsum(A)): A [Kb,M] bf16, B [Kb,N] bf16;
 // outputs fp32 (master-grad dtype).  with_db=false skips db.
 std::tuple<torch::Tensor, c10::optional<torch::Tensor>> hip_gemm_kt_bf16(
@@ -687,29 +714,21 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> hip_gemm_kt_bf16(
   TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(0) == B.size(0),
               "shape mismatch");
   const int64_t Kb = A.size(0), M = A.size(1), N = B.size(1);
-  auto Ac = A.contiguous();
-  auto Bc = B.contiguous();
-  // 128x128/8-wave tiles for big dW shapes (halves the A/B re-read
-  // amplification); 64x64 for small/tail-heavy outputs
-  const bool big = (M >= KBM && N >= 96 && Kb >= 4096);
-  const int64_t bm = big ? KBM : GBM, bn = big ? KBN : GBN;
-  const int64_t m_t = (M + bm - 1) / bm, n_t = (N + bn - 1) / bn;
-  // split-K sized so the grid fills the 256 CUs a few times over
-  int64_t z = 1;
-  if (Kb > GBK) {
-    const int64_t want_wg = big ? 512 : 1024;
-    const int64_t want = (want_wg + m_t * n_t - 1) / (m_t * n_t);
-    const int64_t max_z = (Kb + GBK - 1) / GBK;
-    z = std::max<int64_t>(1, std::min(want, max_z));
-  }
-  const int64_t k_per_z = ((Kb + z - 1) / z + GBK - 1) / GBK * GBK;
-  z = std::max<int64_t>(1, (Kb + k_per_z - 1) / k_per_z);
   c10::optional<torch::Tensor> db;
   float* db_p = nullptr;
-  if (Kb == 0) {
-    if (with_db) db = torch::zeros({M}, A.options().dtype(torch::kFloat32));
+  // empty reduction or empty output: zeros, before any plan arithmetic
+  // or launch (a grid dimension of 0 is a launch error)
+  if (Kb == 0 || M == 0 || N == 0) {
+    // db = colsum(A) does not depend on N: with an empty dW it is the
+    // only output left, zeros when the reduction itself is empty
+    if (with_db) db = A.sum({0}, /*keepdim=*/false, torch::kFloat32);
     return {torch::zeros({M, N}, A.options().dtype(torch::kFloat32)), db};
   }
+  auto Ac = A.contiguous();
+  auto Bc = B.contiguous();
+  const GemmKtPlan p = gemm_kt_bf16_plan(Kb, M, N);
+  const bool big = p.big;
+  const int64_t m_t = p.m_t, n_t = p.n_t, z = p.z, k_per_z = p.k_per_z;
   // z>1: per-chunk partial planes + one sum(0) (no output atomics).  A
   // plane is C's [M, N] followed, with_db, by the chunk's db row [M]:
   // every (chunk, m) db cell is stored exactly once, by the

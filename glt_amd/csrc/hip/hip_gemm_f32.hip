@@ -275,7 +275,7 @@ torch::Tensor hip_sage_gemm(const torch::Tensor& A, const torch::Tensor& B,
   auto Ac = A.contiguous();
   auto Bc = B.contiguous();
   auto C = torch::empty({M, N}, A.options());
-  if (M == 0) return C;
+  if (M == 0 || N == 0) return C;  // nothing to write, no zero-dim grid
   const float* bias_p =
       bias.has_value() ? bias->data_ptr<float>() : nullptr;
   // the 128x128 tile pays only with enough K depth to amortize its

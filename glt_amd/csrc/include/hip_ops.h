@@ -195,6 +195,13 @@ torch::Tensor hip_gemm_bt_bf16(const torch::Tensor& A,
 // (dW, db) = (A[Kb,M]^T @ B[Kb,N], colsum A), fp32 outputs (split-K).
 std::tuple<torch::Tensor, c10::optional<torch::Tensor>> hip_gemm_kt_bf16(
     const torch::Tensor& A, const torch::Tensor& B, bool with_db);
+// The launcher's own dispatch for a shape: 128x128 (big) or 64x64 tiles,
+// output tile counts, split-K chunks z of k_per_z rows each.
+struct GemmKtPlan {
+  bool big;
+  int64_t m_t, n_t, z, k_per_z;
+};
+GemmKtPlan gemm_kt_bf16_plan(int64_t Kb, int64_t M, int64_t N);
 torch::Tensor hip_mfma_bf16_selftest(const torch::Tensor& A,
                                      const torch::Tensor& B);
 
