@@ -41,9 +41,14 @@ namespace glt {
 
 namespace {
 
-// out[t, :] = mean_{e in [off[t], off[t+1])} x[col[e], :]
+// out[t, :F] = mean_{e in [off[t], off[t+1])} x[col[e], :]
 // One wave per target row; lanes cover the feature dim.
-template <typename scalar_t>
+// kCat: out is [n_tgt, 2F] and out[t, F:] = x[t, :], the fused
+// [mean-agg | x_root] assembly.  Saves the dim-1 torch.cat (two copyBuffer
+// passes over [n, F] per layer, ~260 us/step in the flagship profile) and
+// its launches; valid for the homo SAGE path where targets are the row
+// prefix of x (the sampler's local-id invariant).
+template <typename scalar_t, bool kCat>
 __global__ void seg_mean_fwd_kernel(const scalar_t* __restrict__ x,
                                     const int64_t* __restrict__ col,
                                     const int64_t* __restrict__ off,
@@ -53,6 +58,7 @@ __global__ void seg_mean_fwd_kernel(const scalar_t* __restrict__ x,
   const int64_t wave =
       (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
   const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int64_t ostride = kCat ? 2 * feat : feat;
   for (int64_t t = wave; t < n_tgt; t += n_waves) {
     const int64_t s = off[t], e = off[t + 1];
     const float inv = e > s ? 1.0f / (float)(e - s) : 0.0f;
@@ -75,15 +81,22 @@ __global__ void seg_mean_fwd_kernel(const scalar_t* __restrict__ x,
           }
         }
       }
-      if (f0 < feat) out[t * feat + f0] = static_cast<scalar_t>(a0 * inv);
-      if (f1 < feat) out[t * feat + f1] = static_cast<scalar_t>(a1 * inv);
+      if (f0 < feat) {
+        out[t * ostride + f0] = static_cast<scalar_t>(a0 * inv);
+        if constexpr (kCat) out[t * ostride + feat + f0] = x[t * feat + f0];
+      }
+      if (f1 < feat) {
+        out[t * ostride + f1] = static_cast<scalar_t>(a1 * inv);
+        if constexpr (kCat) out[t * ostride + feat + f1] = x[t * feat + f1];
+      }
       continue;
     }
     for (int64_t f = lane; f < feat; f += kWave) {
       float acc = 0.f;
       for (int64_t k = s; k < e; ++k)
         acc += static_cast<float>(x[col[k] * feat + f]);
-      out[t * feat + f] = static_cast<scalar_t>(acc * inv);
+      out[t * ostride + f] = static_cast<scalar_t>(acc * inv);
+      if constexpr (kCat) out[t * ostride + feat + f] = x[t * feat + f];
     }
   }
 }
@@ -91,6 +104,7 @@ __global__ void seg_mean_fwd_kernel(const scalar_t* __restrict__ x,
 // bf16 fast path: each lane owns TWO adjacent channels (one 4-byte
 // ushort2 load per row visit) — the scalar template's 2-byte gathers
 // were measured at only 1.36x fp32 on the HBM-bound forward.
+template <bool kCat>
 __global__ void seg_mean_fwd_bf162_kernel(const __hip_bfloat162* __restrict__ x,
                                           const int64_t* __restrict__ col,
                                           const int64_t* __restrict__ off,
@@ -100,6 +114,7 @@ __global__ void seg_mean_fwd_bf162_kernel(const __hip_bfloat162* __restrict__ x,
   const int64_t wave =
       (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
   const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int64_t ostride = kCat ? 2 * feat2 : feat2;
   for (int64_t t = wave; t < n_tgt; t += n_waves) {
     const int64_t s = off[t], e = off[t + 1];
     const float inv = e > s ? 1.0f / (float)(e - s) : 0.0f;
@@ -125,59 +140,10 @@ __global__ void seg_mean_fwd_bf162_kernel(const __hip_bfloat162* __restrict__ x,
           }
         }
       }
-      if (act)
-        out[t * feat2 + f] =
-            __float22bfloat162_rn({acc.x * inv, acc.y * inv});
-      continue;
-    }
-    for (int64_t f = lane; f < feat2; f += kWave) {
-      float2 acc = {0.f, 0.f};
-      for (int64_t k = s; k < e; ++k) {
-        const float2 v = __bfloat1622float2(x[col[k] * feat2 + f]);
-        acc.x += v.x;
-        acc.y += v.y;
-      }
-      out[t * feat2 + f] =
-          __float22bfloat162_rn({acc.x * inv, acc.y * inv});
-    }
-  }
-}
-
-__global__ void seg_mean_cat_fwd_bf162_kernel(
-    const __hip_bfloat162* __restrict__ x,
-    const int64_t* __restrict__ col, const int64_t* __restrict__ off,
-    int64_t n_tgt, int64_t feat2, __hip_bfloat162* __restrict__ out) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t wave =
-      (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
-  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  const int64_t ostride = 2 * feat2;
-  for (int64_t t = wave; t < n_tgt; t += n_waves) {
-    const int64_t s = off[t], e = off[t + 1];
-    const float inv = e > s ? 1.0f / (float)(e - s) : 0.0f;
-    if (feat2 <= kWave) {
-      const int64_t f = lane;
-      const bool act = f < feat2;
-      float2 acc = {0.f, 0.f};
-      for (int64_t k0 = s; k0 < e; k0 += 8) {
-        const int nb = (int)((e - k0) < 8 ? (e - k0) : 8);
-        int64_t cc[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-          cc[q] = (q < nb ? col[k0 + q] : col[k0]) * feat2;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          if (q < nb && act) {
-            const float2 v = __bfloat1622float2(x[cc[q] + f]);
-            acc.x += v.x;
-            acc.y += v.y;
-          }
-        }
-      }
       if (act) {
         out[t * ostride + f] =
             __float22bfloat162_rn({acc.x * inv, acc.y * inv});
-        out[t * ostride + feat2 + f] = x[t * feat2 + f];
+        if constexpr (kCat) out[t * ostride + feat2 + f] = x[t * feat2 + f];
       }
       continue;
     }
@@ -190,7 +156,7 @@ __global__ void seg_mean_cat_fwd_bf162_kernel(
       }
       out[t * ostride + f] =
           __float22bfloat162_rn({acc.x * inv, acc.y * inv});
-      out[t * ostride + feat2 + f] = x[t * feat2 + f];
+      if constexpr (kCat) out[t * ostride + feat2 + f] = x[t * feat2 + f];
     }
   }
 }
@@ -262,110 +228,29 @@ __device__ __forceinline__ float snap(float v, float magic) {
   return magic == 0.f ? v : __fsub_rn(__fadd_rn(v, magic), magic);
 }
 
-// dx[col[e], :] += dy[t, :] / deg(t)  (dx is always fp32)
-template <typename scalar_t>
+// dx[col[e], :] += dy[t, :F] / deg(t)  (dx is always fp32)
+// kCat: dy is [n_tgt, 2F] and dx[t, :] += dy[t, F:] as well
+template <typename scalar_t, bool kCat>
 __global__ void seg_mean_bwd_kernel(const scalar_t* __restrict__ dy,
                                     const int64_t* __restrict__ col,
                                     const int64_t* __restrict__ off,
                                     int64_t n_tgt, int64_t feat,
                                     const float* __restrict__ amax_parts,
-    int n_parts,
+                                    int n_parts,
                                     float* __restrict__ dx) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t wave =
       (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
   const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int64_t ostride = kCat ? 2 * feat : feat;
   const float magic = grid_magic(amax_parts, n_parts);
   for (int64_t t = wave; t < n_tgt; t += n_waves) {
     const int64_t s = off[t], e = off[t + 1];
-    if (e <= s) continue;
-    const float inv = 1.0f / (float)(e - s);
-    for (int64_t k = s; k < e; ++k) {
-      const int64_t c = col[k];
-      for (int64_t f = lane; f < feat; f += kWave) {
-        atomicAdd(&dx[c * feat + f],
-                  snap(static_cast<float>(dy[t * feat + f]) * inv, magic));
-      }
+    if constexpr (kCat) {
+      for (int64_t f = lane; f < feat; f += kWave)
+        atomicAdd(&dx[t * feat + f],
+                  snap(static_cast<float>(dy[t * ostride + feat + f]), magic));
     }
-  }
-}
-
-// Fused [mean-agg | x_root] assembly: out[t, :F] = segment mean,
-// out[t, F:] = x[t, :].  Saves the dim-1 torch.cat (two copyBuffer passes
-// over [n, F] per layer, ~260 us/step in the flagship profile) and its
-// launches; valid for the homo SAGE path where targets are the row prefix
-// of x (the sampler's local-id invariant).
-template <typename scalar_t>
-__global__ void seg_mean_cat_fwd_kernel(const scalar_t* __restrict__ x,
-                                        const int64_t* __restrict__ col,
-                                        const int64_t* __restrict__ off,
-                                        int64_t n_tgt, int64_t feat,
-                                        scalar_t* __restrict__ out) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t wave =
-      (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
-  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  const int64_t ostride = 2 * feat;
-  for (int64_t t = wave; t < n_tgt; t += n_waves) {
-    const int64_t s = off[t], e = off[t + 1];
-    const float inv = e > s ? 1.0f / (float)(e - s) : 0.0f;
-    if (feat <= 2 * kWave) {
-      const int64_t f0 = lane, f1 = lane + kWave;
-      float a0 = 0.f, a1 = 0.f;
-      for (int64_t k0 = s; k0 < e; k0 += 8) {
-        const int nb = (int)((e - k0) < 8 ? (e - k0) : 8);
-        int64_t cc[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-          cc[q] = (q < nb ? col[k0 + q] : col[k0]) * feat;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          if (q < nb) {
-            if (f0 < feat) a0 += static_cast<float>(x[cc[q] + f0]);
-            if (f1 < feat) a1 += static_cast<float>(x[cc[q] + f1]);
-          }
-        }
-      }
-      if (f0 < feat) {
-        out[t * ostride + f0] = static_cast<scalar_t>(a0 * inv);
-        out[t * ostride + feat + f0] = x[t * feat + f0];
-      }
-      if (f1 < feat) {
-        out[t * ostride + f1] = static_cast<scalar_t>(a1 * inv);
-        out[t * ostride + feat + f1] = x[t * feat + f1];
-      }
-      continue;
-    }
-    for (int64_t f = lane; f < feat; f += kWave) {
-      float acc = 0.f;
-      for (int64_t k = s; k < e; ++k)
-        acc += static_cast<float>(x[col[k] * feat + f]);
-      out[t * ostride + f] = static_cast<scalar_t>(acc * inv);
-      out[t * ostride + feat + f] = x[t * feat + f];
-    }
-  }
-}
-
-// dx[t, :] += dy[t, F:];  dx[col[e], :] += dy[t, :F] / deg(t)
-template <typename scalar_t>
-__global__ void seg_mean_cat_bwd_kernel(const scalar_t* __restrict__ dy,
-                                        const int64_t* __restrict__ col,
-                                        const int64_t* __restrict__ off,
-                                        int64_t n_tgt, int64_t feat,
-                                        const float* __restrict__ amax_parts,
-    int n_parts,
-                                        float* __restrict__ dx) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t wave =
-      (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave;
-  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  const int64_t ostride = 2 * feat;
-  const float magic = grid_magic(amax_parts, n_parts);
-  for (int64_t t = wave; t < n_tgt; t += n_waves) {
-    const int64_t s = off[t], e = off[t + 1];
-    for (int64_t f = lane; f < feat; f += kWave)
-      atomicAdd(&dx[t * feat + f],
-                snap(static_cast<float>(dy[t * ostride + feat + f]), magic));
     if (e <= s) continue;
     const float inv = 1.0f / (float)(e - s);
     for (int64_t k = s; k < e; ++k) {
@@ -639,73 +524,58 @@ int wave_grid(int64_t rows) {
     }                                                              \
   }()
 
-}  // namespace
-
-torch::Tensor hip_segment_mean_fwd(const torch::Tensor& x,
-                                   const torch::Tensor& col,
-                                   const torch::Tensor& offsets,
-                                   int64_t n_tgt) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous(),
-              "segment_mean: x must be contiguous on device");
-  const int64_t feat = x.size(1);
-  auto out = torch::empty({n_tgt, feat}, x.options());
-  if (n_tgt > 0) {
-    if (x.scalar_type() == torch::kBFloat16 && feat % 2 == 0) {
-      hipLaunchKernelGGL(seg_mean_fwd_bf162_kernel,
-                         dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
-                         current_stream(),
-                         reinterpret_cast<const __hip_bfloat162*>(
-                             x.data_ptr()),
-                         col.data_ptr<int64_t>(),
-                         offsets.data_ptr<int64_t>(), n_tgt, feat / 2,
-                         reinterpret_cast<__hip_bfloat162*>(
-                             out.data_ptr()));
-      return out;
-    }
-    GLT_DISPATCH_SEG(x.scalar_type(), "segment_mean_fwd", [&] {
-      hipLaunchKernelGGL(seg_mean_fwd_kernel<scalar_t>,
-                         dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
-                         current_stream(), x.data_ptr<scalar_t>(),
-                         col.data_ptr<int64_t>(),
-                         offsets.data_ptr<int64_t>(), n_tgt, feat,
-                         out.data_ptr<scalar_t>());
-    });
-  }
-  return out;
+// x or dy of an entry point: [rows, F], fp32 or bf16, on the device
+void check_values(const torch::Tensor& v, const char* what,
+                  bool contiguous) {
+  TORCH_CHECK(v.is_cuda() && v.dim() == 2 &&
+                  (v.scalar_type() == torch::kFloat32 ||
+                   v.scalar_type() == torch::kBFloat16),
+              "segment: ", what, " must be a 2-D fp32/bf16 tensor on device");
+  TORCH_CHECK(!contiguous || v.is_contiguous(),
+              "segment: ", what, " must be contiguous");
 }
 
-torch::Tensor hip_segment_mean_cat_fwd(const torch::Tensor& x,
-                                       const torch::Tensor& col,
-                                       const torch::Tensor& offsets,
-                                       int64_t n_tgt) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous(),
-              "segment_mean_cat: x must be contiguous on device");
-  TORCH_CHECK(x.size(0) >= n_tgt,
+// col / offsets of an entry point: the kernels read offsets[0 .. n_tgt]
+// and col[offsets[0] .. offsets[n_tgt])
+void check_index(const torch::Tensor& col, const torch::Tensor& offsets,
+                 int64_t n_tgt) {
+  TORCH_CHECK(col.is_cuda() && col.is_contiguous() &&
+                  col.scalar_type() == torch::kInt64 && offsets.is_cuda() &&
+                  offsets.is_contiguous() &&
+                  offsets.scalar_type() == torch::kInt64,
+              "segment: col/offsets must be contiguous int64 on device");
+  TORCH_CHECK(n_tgt >= 0 && offsets.numel() == n_tgt + 1,
+              "segment: offsets must have n_tgt + 1 entries");
+}
+
+template <bool kCat>
+torch::Tensor segment_mean_fwd(const torch::Tensor& x,
+                               const torch::Tensor& col,
+                               const torch::Tensor& offsets, int64_t n_tgt) {
+  check_values(x, "x", true);
+  check_index(col, offsets, n_tgt);
+  TORCH_CHECK(!kCat || x.size(0) >= n_tgt,
               "segment_mean_cat: targets must be a row prefix of x");
   const int64_t feat = x.size(1);
-  auto out = torch::empty({n_tgt, 2 * feat}, x.options());
-  if (n_tgt > 0) {
-    if (x.scalar_type() == torch::kBFloat16 && feat % 2 == 0) {
-      hipLaunchKernelGGL(seg_mean_cat_fwd_bf162_kernel,
-                         dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
-                         current_stream(),
-                         reinterpret_cast<const __hip_bfloat162*>(
-                             x.data_ptr()),
-                         col.data_ptr<int64_t>(),
-                         offsets.data_ptr<int64_t>(), n_tgt, feat / 2,
-                         reinterpret_cast<__hip_bfloat162*>(
-                             out.data_ptr()));
-      return out;
-    }
-    GLT_DISPATCH_SEG(x.scalar_type(), "segment_mean_cat_fwd", [&] {
-      hipLaunchKernelGGL(seg_mean_cat_fwd_kernel<scalar_t>,
-                         dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
-                         current_stream(), x.data_ptr<scalar_t>(),
-                         col.data_ptr<int64_t>(),
-                         offsets.data_ptr<int64_t>(), n_tgt, feat,
-                         out.data_ptr<scalar_t>());
-    });
+  auto out = torch::empty({n_tgt, kCat ? 2 * feat : feat}, x.options());
+  if (n_tgt == 0 || feat == 0) return out;
+  if (x.scalar_type() == torch::kBFloat16 && feat % 2 == 0) {
+    hipLaunchKernelGGL(seg_mean_fwd_bf162_kernel<kCat>,
+                       dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
+                       current_stream(),
+                       reinterpret_cast<const __hip_bfloat162*>(x.data_ptr()),
+                       col.data_ptr<int64_t>(), offsets.data_ptr<int64_t>(),
+                       n_tgt, feat / 2,
+                       reinterpret_cast<__hip_bfloat162*>(out.data_ptr()));
+    return out;
   }
+  GLT_DISPATCH_SEG(x.scalar_type(), "segment_mean_fwd", [&] {
+    hipLaunchKernelGGL((seg_mean_fwd_kernel<scalar_t, kCat>),
+                       dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
+                       current_stream(), x.data_ptr<scalar_t>(),
+                       col.data_ptr<int64_t>(), offsets.data_ptr<int64_t>(),
+                       n_tgt, feat, out.data_ptr<scalar_t>());
+  });
   return out;
 }
 
@@ -741,60 +611,38 @@ BwdArena make_bwd_arena(const torch::Tensor& dyc, int64_t n_src,
 
 // Returns fp32 regardless of dy dtype (fp32 atomic accumulation arena);
 // the python wrapper casts to dy.dtype once.
-torch::Tensor hip_segment_mean_cat_bwd(const torch::Tensor& dy,
-                                       const torch::Tensor& col,
-                                       const torch::Tensor& offsets,
-                                       int64_t n_src,
-                                       bool order_independent) {
+template <bool kCat>
+torch::Tensor segment_mean_bwd(const torch::Tensor& dy,
+                               const torch::Tensor& col,
+                               const torch::Tensor& offsets, int64_t n_src,
+                               bool order_independent) {
+  check_values(dy, "dy", false);
   const int64_t n_tgt = dy.size(0);
-  const int64_t feat = dy.size(1) / 2;
-  torch::Tensor dx;
-  if (n_tgt == 0)
-    return torch::zeros({n_src, feat}, dy.options().dtype(torch::kFloat32));
-  {
-    auto dyc = dy.contiguous();
-    GLT_DISPATCH_SEG(dy.scalar_type(), "segment_mean_cat_bwd", [&] {
-      auto arena = make_bwd_arena<scalar_t>(dyc, n_src, feat,
-                                            order_independent);
-      dx = arena.dx;
-      hipLaunchKernelGGL(seg_mean_cat_bwd_kernel<scalar_t>,
-                         dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
-                         current_stream(), dyc.data_ptr<scalar_t>(),
-                         col.data_ptr<int64_t>(),
-                         offsets.data_ptr<int64_t>(), n_tgt, feat,
-                         arena.parts, arena.n_parts, dx.data_ptr<float>());
-    });
+  check_index(col, offsets, n_tgt);
+  if (kCat) {
+    TORCH_CHECK(dy.size(1) % 2 == 0,
+                "segment_mean_cat: dy must have an even number of columns");
+    TORCH_CHECK(n_src >= n_tgt,
+                "segment_mean_cat: targets must be a row prefix of x");
   }
+  const int64_t feat = kCat ? dy.size(1) / 2 : dy.size(1);
+  if (n_tgt == 0 || feat == 0)
+    return torch::zeros({n_src, feat}, dy.options().dtype(torch::kFloat32));
+  auto dyc = dy.contiguous();
+  torch::Tensor dx;
+  GLT_DISPATCH_SEG(dy.scalar_type(), "segment_mean_bwd", [&] {
+    auto arena = make_bwd_arena<scalar_t>(dyc, n_src, feat,
+                                          order_independent);
+    dx = arena.dx;
+    hipLaunchKernelGGL((seg_mean_bwd_kernel<scalar_t, kCat>),
+                       dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
+                       current_stream(), dyc.data_ptr<scalar_t>(),
+                       col.data_ptr<int64_t>(), offsets.data_ptr<int64_t>(),
+                       n_tgt, feat, arena.parts, arena.n_parts,
+                       dx.data_ptr<float>());
+  });
   return dx;
 }
-
-torch::Tensor hip_segment_mean_bwd(const torch::Tensor& dy,
-                                   const torch::Tensor& col,
-                                   const torch::Tensor& offsets,
-                                   int64_t n_src, bool order_independent) {
-  const int64_t n_tgt = dy.size(0);
-  const int64_t feat = dy.size(1);
-  torch::Tensor dx;
-  if (n_tgt == 0)
-    return torch::zeros({n_src, feat}, dy.options().dtype(torch::kFloat32));
-  {
-    auto dyc = dy.contiguous();
-    GLT_DISPATCH_SEG(dy.scalar_type(), "segment_mean_bwd", [&] {
-      auto arena = make_bwd_arena<scalar_t>(dyc, n_src, feat,
-                                            order_independent);
-      dx = arena.dx;
-      hipLaunchKernelGGL(seg_mean_bwd_kernel<scalar_t>,
-                         dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
-                         current_stream(), dyc.data_ptr<scalar_t>(),
-                         col.data_ptr<int64_t>(),
-                         offsets.data_ptr<int64_t>(), n_tgt, feat,
-                         arena.parts, arena.n_parts, dx.data_ptr<float>());
-    });
-  }
-  return dx;
-}
-
-namespace {
 
 // optional fp32 factor of the weighted segment sum -> device pointer
 const float* wsum_factor(const c10::optional<torch::Tensor>& t, int64_t n,
@@ -807,18 +655,36 @@ const float* wsum_factor(const c10::optional<torch::Tensor>& t, int64_t n,
   return t->data_ptr<float>();
 }
 
-void wsum_check_index(const torch::Tensor& col, const torch::Tensor& offsets,
-                      int64_t n_tgt) {
-  TORCH_CHECK(col.is_cuda() && col.is_contiguous() &&
-                  col.scalar_type() == torch::kInt64 && offsets.is_cuda() &&
-                  offsets.is_contiguous() &&
-                  offsets.scalar_type() == torch::kInt64,
-              "segment_wsum: col/offsets must be contiguous int64 on device");
-  TORCH_CHECK(offsets.numel() == n_tgt + 1,
-              "segment_wsum: offsets must have n_tgt + 1 entries");
+}  // namespace
+
+torch::Tensor hip_segment_mean_fwd(const torch::Tensor& x,
+                                   const torch::Tensor& col,
+                                   const torch::Tensor& offsets,
+                                   int64_t n_tgt) {
+  return segment_mean_fwd<false>(x, col, offsets, n_tgt);
 }
 
-}  // namespace
+torch::Tensor hip_segment_mean_cat_fwd(const torch::Tensor& x,
+                                       const torch::Tensor& col,
+                                       const torch::Tensor& offsets,
+                                       int64_t n_tgt) {
+  return segment_mean_fwd<true>(x, col, offsets, n_tgt);
+}
+
+torch::Tensor hip_segment_mean_bwd(const torch::Tensor& dy,
+                                   const torch::Tensor& col,
+                                   const torch::Tensor& offsets,
+                                   int64_t n_src, bool order_independent) {
+  return segment_mean_bwd<false>(dy, col, offsets, n_src, order_independent);
+}
+
+torch::Tensor hip_segment_mean_cat_bwd(const torch::Tensor& dy,
+                                       const torch::Tensor& col,
+                                       const torch::Tensor& offsets,
+                                       int64_t n_src,
+                                       bool order_independent) {
+  return segment_mean_bwd<true>(dy, col, offsets, n_src, order_independent);
+}
 
 // absent edge weight / source scale -> compile-time flags (no ones tensor,
 // no per-edge branch)
@@ -848,11 +714,10 @@ torch::Tensor hip_segment_wsum_fwd(const torch::Tensor& x,
                                    const c10::optional<torch::Tensor>& w,
                                    const c10::optional<torch::Tensor>& a,
                                    const c10::optional<torch::Tensor>& b) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2,
-              "segment_wsum: x must be a contiguous [n_src, F] device tensor");
+  check_values(x, "x", true);
   const int64_t n_tgt = offsets.numel() - 1;
   const int64_t feat = x.size(1);
-  wsum_check_index(col, offsets, n_tgt);
+  check_index(col, offsets, n_tgt);
   const float* wp = wsum_factor(w, col.numel(), "edge weight");
   const float* ap = wsum_factor(a, n_tgt, "target scale");
   const float* bp = wsum_factor(b, x.size(0), "source scale");
@@ -905,12 +770,11 @@ hip_segment_wsum_bwd(const torch::Tensor& dy,
                      const c10::optional<torch::Tensor>& b, int64_t n_src,
                      bool need_dx, bool need_dw, bool order_independent,
                      const c10::optional<torch::Tensor>& coef_bound) {
-  TORCH_CHECK(dy.is_cuda() && dy.dim() == 2,
-              "segment_wsum_bwd: dy must be a [n_tgt, F] device tensor");
+  check_values(dy, "dy", false);
   const int64_t n_tgt = dy.size(0);
   const int64_t feat = dy.size(1);
   const int64_t n_edge = col.numel();
-  wsum_check_index(col, offsets, n_tgt);
+  check_index(col, offsets, n_tgt);
   const float* wp = wsum_factor(w, n_edge, "edge weight");
   const float* ap = wsum_factor(a, n_tgt, "target scale");
   const float* bp = wsum_factor(b, n_src, "source scale");

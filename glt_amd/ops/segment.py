@@ -42,6 +42,18 @@ def _boundaries(n: int, device) -> torch.Tensor:
     return buf[: n + 1]
 
 
+def _offsets(tgt: torch.Tensor, n_tgt: int) -> torch.Tensor:
+    """CSR offsets [n_tgt + 1] of the ascending target ids."""
+    return torch.searchsorted(tgt, _boundaries(n_tgt, tgt.device))
+
+
+def _from_arena(dx, dy):
+    """The backward kernels accumulate in an fp32 arena regardless of dy's
+    dtype; the gradient (None if not asked for) goes back in dy's."""
+    if dx is not None and dx.dtype != dy.dtype:
+        dx = dx.to(dy.dtype)
+    return dx
+
 
 class _SegmentMean(torch.autograd.Function):
     @staticmethod
@@ -57,12 +69,9 @@ class _SegmentMean(torch.autograd.Function):
         from .. import _C
 
         col, offsets = ctx.saved_tensors
-        # kernel accumulates in an fp32 arena regardless of dy dtype
         dx = _C.segment_mean_bwd(dy.contiguous(), col, offsets, ctx.n_src,
                                  is_deterministic())
-        if dx.dtype != dy.dtype:
-            dx = dx.to(dy.dtype)
-        return dx, None, None, None
+        return _from_arena(dx, dy), None, None, None
 
 
 class _SegmentMeanCat(torch.autograd.Function):
@@ -86,9 +95,7 @@ class _SegmentMeanCat(torch.autograd.Function):
         col, offsets = ctx.saved_tensors
         dx = _C.segment_mean_cat_bwd(dy.contiguous(), col, offsets,
                                      ctx.n_src, is_deterministic())
-        if dx.dtype != dy.dtype:
-            dx = dx.to(dy.dtype)
-        return dx, None, None, None
+        return _from_arena(dx, dy), None, None, None
 
 
 def segment_mean(x: torch.Tensor, tgt: torch.Tensor, src: torch.Tensor,
@@ -98,7 +105,7 @@ def segment_mean(x: torch.Tensor, tgt: torch.Tensor, src: torch.Tensor,
     Requires tgt ascending (glt_amd batches satisfy this); returns
     [n_tgt, F].
     """
-    offsets = torch.searchsorted(tgt, _boundaries(n_tgt, tgt.device))
+    offsets = _offsets(tgt, n_tgt)
     return _SegmentMean.apply(x.contiguous(), src.contiguous(), offsets,
                               x.size(0))
 
@@ -107,7 +114,7 @@ def segment_mean_cat(x: torch.Tensor, tgt: torch.Tensor, src: torch.Tensor,
                      n_tgt: int) -> torch.Tensor:
     """[segment_mean | root] fused: returns [n_tgt, 2F] where the left F
     columns are the neighbor mean and the right F columns are x[:n_tgt]."""
-    offsets = torch.searchsorted(tgt, _boundaries(n_tgt, tgt.device))
+    offsets = _offsets(tgt, n_tgt)
     return _SegmentMeanCat.apply(x.contiguous(), src.contiguous(), offsets,
                                  n_tgt)
 
@@ -144,10 +151,7 @@ class _SegmentWeightedSum(torch.autograd.Function):
         dx, dw = _C.segment_wsum_bwd(dy.contiguous(), x, col, offsets, w, a,
                                      b, ctx.n_src, need_dx, need_dw, det,
                                      bound)
-        # kernel accumulates in an fp32 arena regardless of dy dtype
-        if dx is not None and dx.dtype != dy.dtype:
-            dx = dx.to(dy.dtype)
-        return dx, dw, None, None, None, None
+        return _from_arena(dx, dy), dw, None, None, None, None
 
 
 def _wsum_fused(x: torch.Tensor, sorted_by_target: bool) -> bool:
@@ -184,7 +188,7 @@ def segment_weighted_sum(x: torch.Tensor, tgt: torch.Tensor,
             return None if v is None else \
                 v.to(torch.float32).contiguous()
 
-        offsets = torch.searchsorted(tgt, _boundaries(n_tgt, tgt.device))
+        offsets = _offsets(tgt, n_tgt)
         a = f32(tgt_scale)
         if a is not None and a.numel() != n_tgt:
             a = a[:n_tgt].contiguous()
