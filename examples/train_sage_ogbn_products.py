@@ -72,6 +72,9 @@ def main():
                          "kernels, fp32 master weights (accuracy parity: "
                          "profiles/r02_convergence.md)")
     ap.add_argument("--lr", type=float, default=0.003)
+    ap.add_argument("--aggr", type=str, default="mean",
+                    choices=["mean", "max", "min", "sum"],
+                    help="SAGEConv neighbor aggregator")
     args = ap.parse_args()
 
     device = torch.device("cuda", 0) if torch.cuda.is_available() \
@@ -83,7 +86,7 @@ def main():
                             batch_size=args.batch_size, shuffle=True,
                             device=device, to_device=device, prefetch=3)
     model = GraphSAGE(ds.node_features.size(1), args.hidden, len(fanout),
-                      out_channels=47).to(device)
+                      out_channels=47, aggr=args.aggr).to(device)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
 
     for epoch in range(args.epochs):

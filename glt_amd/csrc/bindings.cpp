@@ -281,6 +281,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("a"), py::arg("b"), py::arg("n_src"), py::arg("need_dx"),
         py::arg("need_dw"), py::arg("order_independent") = false,
         py::arg("coef_bound") = py::none());
+  m.def("segment_ext_fwd", &hip_segment_ext_fwd, py::arg("x"),
+        py::arg("col"), py::arg("offsets"), py::arg("n_tgt"),
+        py::arg("is_max"), py::arg("cat"), py::arg("need_arg"));
+  m.def("segment_ext_bwd", &hip_segment_ext_bwd, py::arg("dy"),
+        py::arg("arg"), py::arg("n_src"), py::arg("cat"),
+        py::arg("order_independent") = false);
 
   // Memory plumbing
   m.def("host_mapped_view", &host_mapped_view, py::arg("src"),

@@ -31,6 +31,10 @@
  * seg_wsum_*: the weighted segment sum behind GCNConv and edge weights
  * (out[t] = a[t] * sum_e w[e] * b[col[e]] * x[col[e]]) with its dx and
  * per-edge dw backward; same layout, arena and order-independent mode.
+ *
+ * seg_ext_*: segment max / min with the arg of the first winning edge
+ * (SAGEConv aggr='max' / 'min'); forward in the seg_wsum layout, backward
+ * one atomic per output element into the same arena.
  */
 #include <hip/hip_bf16.h>
 
@@ -502,6 +506,199 @@ __global__ void seg_wsum_bwd_kernel(const scalar_t* __restrict__ dy,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Segment max / min with the arg of the winner (torch_scatter rule):
+//   out[t, f] = max (min) over e in [off[t], off[t+1]) of x[col[e], f]
+//   arg[t, f] = col[e*], e* the FIRST edge of the segment, in edge order,
+//               that attains it
+// The running winner starts as the first edge of the segment (no +-inf or
+// zero sentinel) and is replaced only on a strict compare, so ties keep
+// the earlier edge; a NaN replaces any non-NaN winner and then stays (NaN
+// compares false), so arg is the first NaN edge.  An empty segment gives
+// out = 0, arg = -1.  The forward is a selection: compares run in fp32
+// (exact for bf16 input) and the winner's own bits are stored.
+// kCat: out is [n_tgt, 2F] with out[t, F:] = x[t, :], as in the mean family.
+// kArg = false stores no arg (x needs no gradient).
+// Backward: dx[arg[t, f], f] += dy[t, f], exactly one source row per
+// output element (and dx[t, :] += dy[t, F:] with kCat).
+// ---------------------------------------------------------------------------
+
+template <bool kMax>
+__device__ __forceinline__ bool ext_wins(float v, float best) {
+  return (kMax ? v > best : v < best) || (v != v && best == best);
+}
+
+// Source rows of up to 8 edges starting at k0, in scalar registers.  Slots
+// past the end of the segment repeat edge k0 (a valid row), so the row
+// loads need no branch; the caller masks them by q < nb.
+__device__ __forceinline__ void ext_edge_batch(const int64_t* __restrict__ col,
+                                               int64_t k0, int nb,
+                                               int64_t (&c)[8]) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q) c[q] = col[q < nb ? k0 + q : k0];
+}
+
+__device__ __forceinline__ float ext_value(float v) { return v; }
+__device__ __forceinline__ float ext_value(c10::BFloat16 v) {
+  return __uint_as_float((uint32_t)v.x << 16);
+}
+
+template <typename scalar_t, bool kMax, bool kCat, bool kArg>
+__global__ void seg_ext_fwd_kernel(const scalar_t* __restrict__ x,
+                                   const int64_t* __restrict__ col,
+                                   const int64_t* __restrict__ off,
+                                   int64_t n_tgt, int64_t feat,
+                                   scalar_t* __restrict__ out,
+                                   int32_t* __restrict__ arg) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = wave_uniform(
+      (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave);
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int64_t ostride = kCat ? 2 * feat : feat;
+  for (int64_t t = wave; t < n_tgt; t += n_waves) {
+    const int64_t s = off[t], e = off[t + 1];
+    // 128 channels per pass (lane owns f and f+64), 8 edges per batch.
+    // Lanes past the row end read its last channel and do not store.
+    for (int64_t fb = 0; fb < feat; fb += 2 * kWave) {
+      const int64_t f0 = fb + lane, f1 = fb + lane + kWave;
+      const int64_t g0 = f0 < feat ? f0 : feat - 1;
+      const int64_t g1 = f1 < feat ? f1 : feat - 1;
+      const bool two = fb + kWave < feat;  // wave-uniform
+      scalar_t w0 = static_cast<scalar_t>(0.f), w1 = w0;  // winner's bits
+      float m0 = 0.f, m1 = 0.f;
+      int32_t i0 = -1, i1 = -1;
+      for (int64_t k0 = s; k0 < e; k0 += 8) {
+        const int nb = (int)((e - k0) < 8 ? (e - k0) : 8);
+        const bool first = k0 == s;  // slot 0 of the first batch always wins
+        int64_t c[8];
+        scalar_t v0[8], v1[8];
+        ext_edge_batch(col, k0, nb, c);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v0[q] = x[c[q] * feat + g0];
+        if (two) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q) v1[q] = x[c[q] * feat + g1];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const float u = ext_value(v0[q]);
+          if (q < nb && ((q == 0 && first) || ext_wins<kMax>(u, m0))) {
+            m0 = u;
+            w0 = v0[q];
+            i0 = (int32_t)c[q];
+          }
+        }
+        if (two) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const float u = ext_value(v1[q]);
+            if (q < nb && ((q == 0 && first) || ext_wins<kMax>(u, m1))) {
+              m1 = u;
+              w1 = v1[q];
+              i1 = (int32_t)c[q];
+            }
+          }
+        }
+      }
+      if (f0 < feat) {
+        out[t * ostride + f0] = w0;
+        if constexpr (kArg) arg[t * feat + f0] = i0;
+        if constexpr (kCat) out[t * ostride + feat + f0] = x[t * feat + f0];
+      }
+      if (f1 < feat) {
+        out[t * ostride + f1] = w1;
+        if constexpr (kArg) arg[t * feat + f1] = i1;
+        if constexpr (kCat) out[t * ostride + feat + f1] = x[t * feat + f1];
+      }
+    }
+  }
+}
+
+// bf16 fast path for even F: a lane owns one adjacent channel pair, so a
+// row visit is one 4-byte load and the arg pair one 8-byte store (t * F +
+// 2f is even).  The pair travels as its raw 32 bits: low half = channel
+// 2f, high half = channel 2f + 1.
+template <bool kMax, bool kCat, bool kArg>
+__global__ void seg_ext_fwd_bf162_kernel(const uint32_t* __restrict__ x,
+                                         const int64_t* __restrict__ col,
+                                         const int64_t* __restrict__ off,
+                                         int64_t n_tgt, int64_t feat2,
+                                         uint32_t* __restrict__ out,
+                                         int2* __restrict__ arg) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = wave_uniform(
+      (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave);
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int64_t ostride = kCat ? 2 * feat2 : feat2;
+  for (int64_t t = wave; t < n_tgt; t += n_waves) {
+    const int64_t s = off[t], e = off[t + 1];
+    for (int64_t fb = 0; fb < feat2; fb += kWave) {
+      const int64_t f = fb + lane;
+      const int64_t g = f < feat2 ? f : feat2 - 1;
+      uint32_t wlo = 0, whi = 0;  // winner's bits, each in its own half
+      float mlo = 0.f, mhi = 0.f;
+      int2 idx = {-1, -1};
+      for (int64_t k0 = s; k0 < e; k0 += 8) {
+        const int nb = (int)((e - k0) < 8 ? (e - k0) : 8);
+        const bool first = k0 == s;
+        int64_t c[8];
+        uint32_t v[8];
+        ext_edge_batch(col, k0, nb, c);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = x[c[q] * feat2 + g];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const float ulo = __uint_as_float(v[q] << 16);
+          const float uhi = __uint_as_float(v[q] & 0xffff0000u);
+          const bool take = q == 0 && first;
+          if (q < nb && (take || ext_wins<kMax>(ulo, mlo))) {
+            mlo = ulo;
+            wlo = v[q] & 0xffffu;
+            idx.x = (int32_t)c[q];
+          }
+          if (q < nb && (take || ext_wins<kMax>(uhi, mhi))) {
+            mhi = uhi;
+            whi = v[q] & 0xffff0000u;
+            idx.y = (int32_t)c[q];
+          }
+        }
+      }
+      if (f < feat2) {
+        out[t * ostride + f] = wlo | whi;
+        if constexpr (kArg) arg[t * feat2 + f] = idx;
+        if constexpr (kCat) out[t * ostride + feat2 + f] = x[t * feat2 + f];
+      }
+    }
+  }
+}
+
+// One lane per (t, f): dx[arg[t, f], f] += dy[t, f] where arg >= 0, plus
+// the root term with kCat.  Several targets may pick the same source row,
+// hence the atomics; the terms are the dy values themselves, so the
+// order-independent grid needs no scale.  Reads neither col nor offsets.
+template <typename scalar_t, bool kCat>
+__global__ void seg_ext_bwd_kernel(const scalar_t* __restrict__ dy,
+                                   const int32_t* __restrict__ arg,
+                                   int64_t n_tgt, int64_t feat,
+                                   const float* __restrict__ amax_parts,
+                                   int n_parts, float* __restrict__ dx) {
+  const float magic = grid_magic(amax_parts, n_parts);
+  const int64_t total = n_tgt * feat;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t ostride = kCat ? 2 * feat : feat;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
+       i += stride) {
+    const int64_t t = i / feat, f = i - t * feat;
+    const int32_t a = arg[i];
+    if (a >= 0)
+      atomicAdd(&dx[(int64_t)a * feat + f],
+                snap(static_cast<float>(dy[t * ostride + f]), magic));
+    if constexpr (kCat)
+      atomicAdd(&dx[i],
+                snap(static_cast<float>(dy[t * ostride + feat + f]), magic));
+  }
+}
+
 int wave_grid(int64_t rows) {
   const int64_t waves = std::min<int64_t>(rows, (int64_t)kMaxBlocks * 4);
   return (int)std::min<int64_t>((waves * kWave + kBlock - 1) / kBlock,
@@ -644,6 +841,40 @@ torch::Tensor segment_mean_bwd(const torch::Tensor& dy,
   return dx;
 }
 
+// runtime bool -> compile-time flag: fn(std::true_type{} / std::false_type{})
+template <typename Fn>
+void with_flag(bool v, Fn&& fn) {
+  if (v)
+    fn(std::true_type{});
+  else
+    fn(std::false_type{});
+}
+
+template <bool kMax, bool kCat, bool kArg>
+void segment_ext_fwd_launch(const torch::Tensor& x, const torch::Tensor& col,
+                            const torch::Tensor& offsets, int64_t n_tgt,
+                            torch::Tensor& out, int32_t* argp) {
+  const int64_t feat = x.size(1);
+  if (x.scalar_type() == torch::kBFloat16 && feat % 2 == 0) {
+    hipLaunchKernelGGL((seg_ext_fwd_bf162_kernel<kMax, kCat, kArg>),
+                       dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
+                       current_stream(),
+                       reinterpret_cast<const uint32_t*>(x.data_ptr()),
+                       col.data_ptr<int64_t>(), offsets.data_ptr<int64_t>(),
+                       n_tgt, feat / 2,
+                       reinterpret_cast<uint32_t*>(out.data_ptr()),
+                       reinterpret_cast<int2*>(argp));
+    return;
+  }
+  GLT_DISPATCH_SEG(x.scalar_type(), "segment_ext_fwd", [&] {
+    hipLaunchKernelGGL((seg_ext_fwd_kernel<scalar_t, kMax, kCat, kArg>),
+                       dim3(wave_grid(n_tgt)), dim3(kBlock), 0,
+                       current_stream(), x.data_ptr<scalar_t>(),
+                       col.data_ptr<int64_t>(), offsets.data_ptr<int64_t>(),
+                       n_tgt, feat, out.data_ptr<scalar_t>(), argp);
+  });
+}
+
 // optional fp32 factor of the weighted segment sum -> device pointer
 const float* wsum_factor(const c10::optional<torch::Tensor>& t, int64_t n,
                          const char* what) {
@@ -684,6 +915,74 @@ torch::Tensor hip_segment_mean_cat_bwd(const torch::Tensor& dy,
                                        int64_t n_src,
                                        bool order_independent) {
   return segment_mean_bwd<true>(dy, col, offsets, n_src, order_independent);
+}
+
+// (out, arg): out is [n_tgt, F] ([n_tgt, 2F] with cat) in x's dtype, arg is
+// int32 [n_tgt, F] or None without need_arg.
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> hip_segment_ext_fwd(
+    const torch::Tensor& x, const torch::Tensor& col,
+    const torch::Tensor& offsets, int64_t n_tgt, bool is_max, bool cat,
+    bool need_arg) {
+  check_values(x, "x", true);
+  check_index(col, offsets, n_tgt);
+  TORCH_CHECK(x.size(0) <= (int64_t)INT32_MAX,
+              "segment_ext: arg is int32, x must have fewer than 2^31 rows");
+  TORCH_CHECK(!cat || x.size(0) >= n_tgt,
+              "segment_ext: cat needs the targets as a row prefix of x");
+  const int64_t feat = x.size(1);
+  auto out = torch::empty({n_tgt, cat ? 2 * feat : feat}, x.options());
+  c10::optional<torch::Tensor> arg;
+  if (need_arg)
+    arg = torch::empty({n_tgt, feat}, x.options().dtype(torch::kInt32));
+  if (n_tgt == 0 || feat == 0) return {out, arg};
+  int32_t* argp = need_arg ? arg->data_ptr<int32_t>() : nullptr;
+  with_flag(is_max, [&](auto kMax) {
+    with_flag(cat, [&](auto kCat) {
+      with_flag(need_arg, [&](auto kArg) {
+        segment_ext_fwd_launch<decltype(kMax)::value, decltype(kCat)::value,
+                               decltype(kArg)::value>(x, col, offsets, n_tgt,
+                                                      out, argp);
+      });
+    });
+  });
+  return {out, arg};
+}
+
+// fp32 dx [n_src, F] (accumulation arena; the python wrapper casts once)
+torch::Tensor hip_segment_ext_bwd(const torch::Tensor& dy,
+                                  const torch::Tensor& arg, int64_t n_src,
+                                  bool cat, bool order_independent) {
+  check_values(dy, "dy", false);
+  const int64_t n_tgt = dy.size(0);
+  TORCH_CHECK(!cat || dy.size(1) % 2 == 0,
+              "segment_ext: cat needs a dy with an even number of columns");
+  const int64_t feat = cat ? dy.size(1) / 2 : dy.size(1);
+  TORCH_CHECK(n_src >= 0 && n_src <= (int64_t)INT32_MAX &&
+                  (!cat || n_src >= n_tgt),
+              "segment_ext: n_src must be below 2^31 and, with cat, at "
+              "least n_tgt");
+  TORCH_CHECK(arg.is_cuda() && arg.is_contiguous() &&
+                  arg.scalar_type() == torch::kInt32 && arg.dim() == 2 &&
+                  arg.size(0) == n_tgt && arg.size(1) == feat,
+              "segment_ext: arg must be a contiguous int32 [n_tgt, F] "
+              "tensor on device");
+  if (n_tgt == 0 || feat == 0)
+    return torch::zeros({n_src, feat}, dy.options().dtype(torch::kFloat32));
+  auto dyc = dy.contiguous();
+  torch::Tensor dx;
+  GLT_DISPATCH_SEG(dy.scalar_type(), "segment_ext_bwd", [&] {
+    auto arena = make_bwd_arena<scalar_t>(dyc, n_src, feat,
+                                          order_independent);
+    dx = arena.dx;
+    with_flag(cat, [&](auto kCat) {
+      hipLaunchKernelGGL(
+          (seg_ext_bwd_kernel<scalar_t, decltype(kCat)::value>),
+          dim3(grid_for(n_tgt * feat)), dim3(kBlock), 0, current_stream(),
+          dyc.data_ptr<scalar_t>(), arg.data_ptr<int32_t>(), n_tgt, feat,
+          arena.parts, arena.n_parts, dx.data_ptr<float>());
+    });
+  });
+  return dx;
 }
 
 // absent edge weight / source scale -> compile-time flags (no ones tensor,

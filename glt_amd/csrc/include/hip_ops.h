@@ -138,6 +138,20 @@ hip_segment_wsum_bwd(const torch::Tensor& dy,
                      bool need_dx, bool need_dw, bool order_independent,
                      const c10::optional<torch::Tensor>& coef_bound);
 
+// Segment max / min: out[t, f] = extreme over the segment of x[col[e], f],
+// arg[t, f] = col of the FIRST edge attaining it (strict compare, NaN
+// wins; empty segment: out 0, arg -1).  cat: out is [n_tgt, 2F] with
+// out[t, F:] = x[t, :].  fwd returns (out, arg int32 [n_tgt, F] or None
+// without need_arg); bwd returns fp32 dx with dx[arg[t, f], f] += dy[t, f]
+// (+ dx[t, :] += dy[t, F:] with cat).
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> hip_segment_ext_fwd(
+    const torch::Tensor& x, const torch::Tensor& col,
+    const torch::Tensor& offsets, int64_t n_tgt, bool is_max, bool cat,
+    bool need_arg);
+torch::Tensor hip_segment_ext_bwd(const torch::Tensor& dy,
+                                  const torch::Tensor& arg, int64_t n_src,
+                                  bool cat, bool order_independent);
+
 // --- fused GAT edge softmax + aggregation (hip_gat.hip) ---------------------
 // Attention logits are computed inside the kernels from (h, att) directly.
 // fwd returns (out, m, Z, s_pre); bwd consumes the cached s_pre logits.

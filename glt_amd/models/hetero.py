@@ -262,12 +262,15 @@ class RGNN(nn.Module):
     type, plus a per-node-type self projection so every type advances to
     the layer's output dim even when it receives no messages; ReLU/dropout
     between layers; linear head on the predicted node type.
+    sage_aggr ('mean' | 'max' | 'min' | 'sum') is the neighbor aggregator
+    of the 'rsage' convs.
     """
 
     def __init__(self, etypes: List[EdgeType], in_dim: int, h_dim: int,
                  out_dim: int, num_layers: int = 2, n_heads: int = 4,
                  model: str = "rgat", dropout: float = 0.2,
-                 node_types: Optional[List[NodeType]] = None):
+                 node_types: Optional[List[NodeType]] = None,
+                 sage_aggr: str = "mean"):
         super().__init__()
         self.model = model
         if node_types is None:
@@ -284,7 +287,8 @@ class RGNN(nn.Module):
                                         heads=n_heads, concat=True)
                 else:
                     convs[et] = SAGEConv(dims[li], dims[li + 1],
-                                         root_weight=False)
+                                         root_weight=False,
+                                         aggr=sage_aggr)
             self.layers.append(HeteroConv(convs))
             self.self_lins.append(nn.ModuleDict(
                 {t: nn.Linear(dims[li], dims[li + 1])

@@ -23,18 +23,35 @@ def _degree(target: torch.Tensor, num_nodes: int) -> torch.Tensor:
 
 
 class SAGEConv(nn.Module):
-    """GraphSAGE mean aggregator.
+    """GraphSAGE conv with a mean (default), max, min or sum aggregator.
 
     The neighbor- and root-projections live in ONE [out, 2*in] parameter
     applied to [agg | x]: a single GEMM per layer and no per-step weight
     concatenation (the training step is launch-bound; see profiles/).
+    Parameter names and shapes do not depend on ``aggr``.
+
+    aggr='max' / 'min' follow the torch_scatter rule: the gradient of an
+    output element goes to the one source row of the first edge, in edge
+    order, that attains the extreme (see ops.segment_max); a target
+    without edges aggregates to 0.  On GPU fp32/bf16 batches sorted by
+    target they run the fused HIP kernels, with the [agg | x_root]
+    assembly fused in on the homogeneous path.  aggr='sum' runs
+    ops.segment_sum followed by torch.cat: there is no fused
+    [sum | root] kernel.
     """
 
+    AGGRS = ("mean", "max", "min", "sum")
+
     def __init__(self, in_channels: int, out_channels: int,
-                 root_weight: bool = True, bias: bool = True):
+                 root_weight: bool = True, bias: bool = True,
+                 aggr: str = "mean"):
         super().__init__()
+        if aggr not in self.AGGRS:
+            raise ValueError(
+                f"SAGEConv: aggr must be one of {self.AGGRS}, got {aggr!r}")
         self.in_channels = in_channels
         self.root_weight = root_weight
+        self.aggr = aggr
         self.lin = nn.Linear(2 * in_channels if root_weight else
                              in_channels, out_channels, bias=bias)
 
@@ -44,6 +61,9 @@ class SAGEConv(nn.Module):
         """x: [n, F] or (x_target, x_source) for bipartite relations.
         fuse_relu folds the activation into the projection GEMM epilogue
         (MFMA path); the caller must then skip its own activation."""
+        if self.aggr != "mean":
+            return self._forward_aggr(x, edge_index, num_target,
+                                      sorted_by_target, fuse_relu)
         if isinstance(x, tuple):
             x_tgt, x_src = x
             n = num_target if num_target is not None else x_tgt.size(0)
@@ -84,6 +104,35 @@ class SAGEConv(nn.Module):
             agg = agg / _degree(tgt, n).unsqueeze(1).to(x.dtype)
             xin = torch.cat([agg, x[:n]], dim=1) if self.root_weight \
                 else agg
+        return self._project(xin, fuse_relu)
+
+    def _forward_aggr(self, x, edge_index, num_target, sorted_by_target,
+                      fuse_relu):
+        """max / min / sum.  The ops take the fused kernels under the
+        predicate the mean path uses (GPU, fp32/bf16, sorted_by_target)
+        and a torch composition otherwise."""
+        from .. import ops
+
+        tgt, src = edge_index[0], edge_index[1]
+        bipartite = isinstance(x, tuple)
+        if bipartite:
+            x_tgt, x_src = x
+            fuse_relu = False
+        else:
+            x_tgt = x_src = x
+        n = num_target if num_target is not None else x_tgt.size(0)
+        if self.aggr == "sum":
+            agg = ops.segment_sum(x_src, tgt, src, n, sorted_by_target)
+        elif self.root_weight and not bipartite:
+            op = ops.segment_max_cat if self.aggr == "max" \
+                else ops.segment_min_cat
+            return self._project(op(x_src, tgt, src, n, sorted_by_target),
+                                 fuse_relu)
+        else:
+            op = ops.segment_max if self.aggr == "max" else ops.segment_min
+            agg = op(x_src, tgt, src, n, sorted_by_target)
+        xin = torch.cat([agg, x_tgt[:n]], dim=1) if self.root_weight \
+            else agg
         return self._project(xin, fuse_relu)
 
     def _project(self, xin, fuse_relu: bool):

@@ -32,14 +32,15 @@ def _layer_trim(num_sampled_nodes, num_sampled_edges, num_layers, layer):
 class GraphSAGE(nn.Module):
     def __init__(self, in_channels: int, hidden_channels: int,
                  num_layers: int, out_channels: Optional[int] = None,
-                 dropout: float = 0.0):
+                 dropout: float = 0.0, aggr: str = "mean"):
+        """aggr: 'mean' | 'max' | 'min' | 'sum', passed to every SAGEConv."""
         super().__init__()
         out_channels = out_channels or hidden_channels
         self.convs = nn.ModuleList()
         dims = ([in_channels] + [hidden_channels] * (num_layers - 1) +
                 [out_channels])
         for i in range(num_layers):
-            self.convs.append(SAGEConv(dims[i], dims[i + 1]))
+            self.convs.append(SAGEConv(dims[i], dims[i + 1], aggr=aggr))
         self.dropout = dropout
 
     def forward(self, x, edge_index, num_sampled_nodes=None,

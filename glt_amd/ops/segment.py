@@ -5,6 +5,8 @@ the GPU and edges are sorted by target (the glt_amd sampler's native edge
 order); the layer falls back to torch index_add on CPU or unsorted input.
 segment_weighted_sum: GCNConv's aggregation and the edge-weight
 primitive; picks the kernels or a torch composition itself.
+segment_max / segment_min (+ _cat) and segment_sum: SAGEConv's other
+aggregators; they pick the kernels or a torch composition the same way.
 """
 import torch
 
@@ -119,6 +121,117 @@ def segment_mean_cat(x: torch.Tensor, tgt: torch.Tensor, src: torch.Tensor,
                                  n_tgt)
 
 
+class _SegmentExt(torch.autograd.Function):
+    """segment max / min (plain or fused with the root concat) over the
+    HIP kernels.  Only ``arg`` is kept for the backward, and only when x
+    needs a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, col, offsets, n_tgt, is_max, cat):
+        from .. import _C
+
+        out, arg = _C.segment_ext_fwd(x, col, offsets, n_tgt, is_max, cat,
+                                      ctx.needs_input_grad[0])
+        if arg is not None:
+            ctx.save_for_backward(arg)
+        ctx.n_src = x.size(0)
+        ctx.cat = cat
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .. import _C
+
+        arg, = ctx.saved_tensors
+        dx = _C.segment_ext_bwd(dy.contiguous(), arg, ctx.n_src, ctx.cat,
+                                is_deterministic())
+        return _from_arena(dx, dy), None, None, None, None, None
+
+
+def _segment_ext_arg(x: torch.Tensor, tgt: torch.Tensor, src: torch.Tensor,
+                     n_tgt: int, is_max: bool) -> torch.Tensor:
+    """int64 [n_tgt, F]: per (target, channel) the source row of the first
+    edge, in edge order, that attains the segment extreme; a NaN beats
+    every number; -1 for a target without edges.  Torch composition, any
+    edge order."""
+    E, F = src.numel(), x.size(1)
+    arg = torch.full((n_tgt, F), -1, dtype=torch.long, device=x.device)
+    if E == 0 or F == 0 or n_tgt == 0:
+        return arg
+    with torch.no_grad():
+        vals = x.index_select(0, src)
+        nan = vals.isnan()
+        idx = tgt.unsqueeze(1).expand(E, F)
+        ext = vals.new_zeros(n_tgt, F).scatter_reduce_(
+            0, idx, vals.masked_fill(nan, 0), "amax" if is_max else "amin",
+            include_self=False)
+        has_nan = vals.new_zeros(n_tgt, F).scatter_reduce_(
+            0, idx, nan.to(vals.dtype), "amax", include_self=True) > 0
+        hit = torch.where(has_nan[tgt], nan, (vals == ext[tgt]) & ~nan)
+        pos = torch.arange(E, device=x.device).unsqueeze(1).expand(E, F)
+        first = torch.full((n_tgt, F), E, dtype=torch.long, device=x.device)
+        first.scatter_reduce_(0, idx, torch.where(hit, pos, E), "amin",
+                              include_self=True)
+        found = first < E
+        arg = torch.where(found, src[first.clamp(max=E - 1)], arg)
+    return arg
+
+
+def _segment_ext(x, tgt, src, n_tgt, sorted_by_target, is_max, cat):
+    if _wsum_fused(x, sorted_by_target):
+        return _SegmentExt.apply(x.contiguous(), src.contiguous(),
+                                 _offsets(tgt, n_tgt), n_tgt, is_max, cat)
+    arg = _segment_ext_arg(x, tgt, src, n_tgt, is_max)
+    if x.size(0) == 0:
+        out = x.new_zeros(n_tgt, x.size(1))
+    else:
+        # gather's backward is the gradient rule: one source row per element
+        out = torch.where(arg >= 0, x.gather(0, arg.clamp(min=0)),
+                          x.new_zeros(()))
+    return torch.cat([out, x[:n_tgt]], dim=1) if cat else out
+
+
+def segment_max(x: torch.Tensor, tgt: torch.Tensor, src: torch.Tensor,
+                n_tgt: int, sorted_by_target: bool = True) -> torch.Tensor:
+    """``out[t, f] = max_{e: tgt[e]=t} x[src[e], f]``; returns [n_tgt, F].
+
+    The gradient of ``out[t, f]`` goes to exactly one source row: that of
+    the first edge, in edge order, that attains the maximum (the
+    torch_scatter rule; torch's ``scatter_reduce`` splits it evenly over
+    ties).  The compare is strict and starts from the segment's first
+    edge, a NaN in the segment gives NaN (the gradient goes to the first
+    NaN edge), a target without edges gets 0 and no gradient.  The result
+    is exact: it carries the bits of the winning input.
+
+    GPU fp32/bf16 input with ``sorted_by_target=True`` (tgt ascending, the
+    glt_amd batch order) runs the fused HIP kernels: no [E, F] message
+    tensor, and an fp32-arena backward that follows ``is_deterministic()``.
+    Anything else runs a torch composition with the same semantics.
+    """
+    return _segment_ext(x, tgt, src, n_tgt, sorted_by_target, True, False)
+
+
+def segment_min(x: torch.Tensor, tgt: torch.Tensor, src: torch.Tensor,
+                n_tgt: int, sorted_by_target: bool = True) -> torch.Tensor:
+    """Minimum counterpart of :func:`segment_max`."""
+    return _segment_ext(x, tgt, src, n_tgt, sorted_by_target, False, False)
+
+
+def segment_max_cat(x: torch.Tensor, tgt: torch.Tensor, src: torch.Tensor,
+                    n_tgt: int,
+                    sorted_by_target: bool = True) -> torch.Tensor:
+    """[segment_max | root] fused: returns [n_tgt, 2F], the right F columns
+    are x[:n_tgt] (targets must be the row prefix of x)."""
+    return _segment_ext(x, tgt, src, n_tgt, sorted_by_target, True, True)
+
+
+def segment_min_cat(x: torch.Tensor, tgt: torch.Tensor, src: torch.Tensor,
+                    n_tgt: int,
+                    sorted_by_target: bool = True) -> torch.Tensor:
+    """[segment_min | root] fused; see :func:`segment_max_cat`."""
+    return _segment_ext(x, tgt, src, n_tgt, sorted_by_target, False, True)
+
+
 class _SegmentWeightedSum(torch.autograd.Function):
     """out[t] = a[t] * sum_e w[e] * b[col[e]] * x[col[e]] over the HIP
     kernels; w, a, b are fp32 or None.  Gradients for x and w only."""
@@ -205,3 +318,11 @@ def segment_weighted_sum(x: torch.Tensor, tgt: torch.Tensor,
     if tgt_scale is not None:
         out = out * tgt_scale.to(x.dtype)[:n_tgt].unsqueeze(1)
     return out
+
+
+def segment_sum(x: torch.Tensor, tgt: torch.Tensor, src: torch.Tensor,
+                n_tgt: int, sorted_by_target: bool = True) -> torch.Tensor:
+    """``out[t] = sum_{e: tgt[e]=t} x[src[e]]``: segment_weighted_sum
+    without factors (same kernels, same fallback)."""
+    return segment_weighted_sum(x, tgt, src, n_tgt,
+                                sorted_by_target=sorted_by_target)

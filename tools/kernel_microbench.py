@@ -26,7 +26,9 @@ def build_flagship_shapes(op, device, bf16=False):
     torch.manual_seed(0)
     n_src, n_tgt, E, F = 590_000, 130_000, 890_000, 256
     if op in ("seg_wsum", "seg_wsum_bf16", "gcn_conv",
-              "gcn_conv_composite"):
+              "gcn_conv_composite", "seg_max", "seg_max_cat",
+              "sage_conv_max", "sage_conv_max_composite") or \
+            (bf16 and op in ("seg_mean", "seg_mean_cat")):
         # F=256 fp32, or the bf16 feature-store shape F=100
         if op == "seg_wsum_bf16" or bf16:
             x = torch.randn(n_src, 100, device=device).to(torch.bfloat16)
@@ -104,10 +106,14 @@ def main():
                              "sample_weighted_hub", "gemm_bt_bf16",
                              "gemm_kt_bf16", "seg_mean_cat_bf16",
                              "seg_wsum", "seg_wsum_bf16", "gcn_conv",
-                             "gcn_conv_composite"])
+                             "gcn_conv_composite", "seg_max", "seg_max_cat",
+                             "sage_conv_max", "sage_conv_max_composite"])
     ap.add_argument("--bf16", action="store_true",
-                    help="gcn_conv ops: bf16 input at F=100 (default fp32 "
-                         "at F=256)")
+                    help="gcn_conv, seg_mean, seg_max and sage_conv_max "
+                         "ops: bf16 input at F=100 (default fp32 at F=256)")
+    ap.add_argument("--fwd-only", action="store_true",
+                    help="seg_max ops: time the forward kernel alone (with "
+                         "the arg store) instead of forward + backward")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     args = ap.parse_args()
@@ -157,6 +163,40 @@ def main():
         a = torch.rand(n_tgt, device=device)
         b = torch.rand(x.size(0), device=device)
         fn = lambda: _C.segment_wsum_fwd(x, src, off, w, a, b)
+    elif args.op in ("seg_max", "seg_max_cat"):
+        # forward (with the arg store) + backward, as in a training step
+        from glt_amd.ops.segment import _boundaries
+        x, tgt, src, n_tgt = inp
+        off = torch.searchsorted(tgt, _boundaries(n_tgt, device))
+        cat = args.op == "seg_max_cat"
+        F = x.size(1)
+        dy = torch.randn(n_tgt, 2 * F if cat else F,
+                         device=device).to(x.dtype)
+        fwd = lambda: _C.segment_ext_fwd(x, src, off, n_tgt, True, cat, True)
+        sz = x.element_size()
+        print(f"forward bytes (E*F*{sz} + E*8 + n_tgt*F*({sz}+4)): "
+              f"{src.numel() * (F * sz + 8) + n_tgt * F * (sz + 4)}")
+        if args.fwd_only:
+            fn = fwd
+        else:
+            def fn():
+                _, arg = fwd()
+                _C.segment_ext_bwd(dy, arg, x.size(0), cat, False)
+    elif args.op in ("sage_conv_max", "sage_conv_max_composite"):
+        # SAGEConv(aggr='max') forward + backward with the gradient of x:
+        # fused kernels against the torch composition
+        from glt_amd.models.layers import SAGEConv
+        x, tgt, src, n_tgt = inp
+        x.requires_grad_(True)
+        conv = SAGEConv(x.size(1), 256, aggr="max").to(device)
+        ei = torch.stack([tgt, src])
+        fused = args.op == "sage_conv_max"
+        gy = torch.randn(n_tgt, 256, device=device).to(x.dtype)
+
+        def fn():
+            conv.zero_grad(set_to_none=True)
+            x.grad = None
+            conv(x, ei, n_tgt, sorted_by_target=fused).backward(gy)
     elif args.op in ("gcn_conv", "gcn_conv_composite"):
         # GCNConv forward + backward (weight gradient only, as in layer
         # 1): fused aggregation against the torch composition
