@@ -190,6 +190,47 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       py::arg("edge_ids") = py::none(), py::arg("edge_weights") = py::none(),
       py::arg("with_edge") = false, py::arg("weighted") = false,
       py::arg("replace") = true);
+  m.def(
+      "sample_neighbors_temporal",
+      [](const torch::Tensor& indptr, const torch::Tensor& indices,
+         const torch::Tensor& seeds, const torch::Tensor& seed_time,
+         int64_t k, const OptTensor& edge_ids, const OptTensor& edge_time,
+         const OptTensor& node_time, bool with_edge, bool last) {
+        return indptr.is_cuda()
+                   ? hip_sample_neighbors_temporal(
+                         indptr, indices, edge_ids, seeds, seed_time,
+                         edge_time, node_time, k, with_edge, last)
+                   : cpu_sample_neighbors_temporal(
+                         indptr, indices, edge_ids, seeds, seed_time,
+                         edge_time, node_time, k, with_edge, last);
+      },
+      py::arg("indptr"), py::arg("indices"), py::arg("seeds"),
+      py::arg("seed_time"), py::arg("k"), py::arg("edge_ids") = py::none(),
+      py::arg("edge_time") = py::none(), py::arg("node_time") = py::none(),
+      py::arg("with_edge") = false, py::arg("last") = false);
+  // Host twins of the device Feistel permutation, element-wise over `j`
+  // (for the CPU round-trip test of feistel_perm_inv).
+  m.def(
+      "feistel_perm_host",
+      [](uint64_t key, const torch::Tensor& j, int64_t n, bool inverse) {
+        check_int64_1d(j, "j");
+        TORCH_CHECK(!j.is_cuda() && j.is_contiguous() && n >= 1,
+                    "feistel_perm_host: contiguous host tensor, n >= 1");
+        auto out = torch::empty_like(j);
+        const int64_t* jp = j.data_ptr<int64_t>();
+        int64_t* op = out.data_ptr<int64_t>();
+        for (int64_t i = 0; i < j.numel(); ++i) {
+          TORCH_CHECK(jp[i] >= 0 && jp[i] < n, "j must be in [0, n)");
+          op[i] = (int64_t)(inverse
+                                ? feistel_perm_inv_host(key, (uint64_t)jp[i],
+                                                        (uint64_t)n)
+                                : feistel_perm_host(key, (uint64_t)jp[i],
+                                                    (uint64_t)n));
+        }
+        return out;
+      },
+      py::arg("key"), py::arg("j"), py::arg("n"),
+      py::arg("inverse") = false);
   m.def("lookup_degree", &lookup_degree);
   m.def("sample_negative", &sample_negative, py::arg("indptr"),
         py::arg("indices"), py::arg("num_cols"), py::arg("req_num"),

@@ -16,6 +16,9 @@
 
 #include <algorithm>
 #include <cmath>
+#include <functional>
+#include <limits>
+#include <utility>
 #include <vector>
 
 namespace glt {
@@ -172,6 +175,123 @@ cpu_sample_neighbors(const torch::Tensor& indptr, const torch::Tensor& indices,
     }
   });
 
+  return {nbrs, nbrs_num,
+          with_edge ? c10::optional<torch::Tensor>(out_eids) : c10::nullopt};
+}
+
+// Temporal one-hop sample, CPU twin of hip_sample_neighbors_temporal: edge
+// position q of row seeds[i] is a candidate iff time(q) <= seed_time[i].
+// Meets the same contract as the HIP kernels (counts, the p <= k output and
+// the whole 'last' output are identical); only which k-subset 'uniform'
+// draws differs (Floyd over the valid positions).
+std::tuple<torch::Tensor, torch::Tensor, c10::optional<torch::Tensor>>
+cpu_sample_neighbors_temporal(const torch::Tensor& indptr,
+                              const torch::Tensor& indices,
+                              const c10::optional<torch::Tensor>& edge_ids,
+                              const torch::Tensor& seeds,
+                              const torch::Tensor& seed_time,
+                              const c10::optional<torch::Tensor>& edge_time,
+                              const c10::optional<torch::Tensor>& node_time,
+                              int64_t k, bool with_edge, bool last) {
+  check_temporal_args(indptr, indices, edge_ids, seeds, seed_time, edge_time,
+                      node_time, with_edge);
+  TORCH_CHECK(!indptr.is_cuda(),
+              "cpu_sample_neighbors_temporal: host tensors required");
+  const auto view = make_view(indptr, indices, edge_ids, c10::nullopt);
+  const bool by_edge = edge_time.has_value();
+  const torch::Tensor& times_t = by_edge ? *edge_time : *node_time;
+  const int64_t* times = times_t.data_ptr<int64_t>();
+  const int64_t n_time = times_t.numel();
+  const int64_t bs = seeds.size(0);
+  const int64_t* seed_ptr = seeds.data_ptr<int64_t>();
+  const int64_t* st_ptr = seed_time.data_ptr<int64_t>();
+  const int64_t kk = k < 0 ? std::numeric_limits<int64_t>::max() : k;
+
+  // time of position q, or false when it has none (node-time source and a
+  // neighbour id outside node_time)
+  auto valid = [&](int64_t q, int64_t t, int64_t& tq) {
+    if (by_edge) {
+      tq = times[q];
+    } else {
+      const int64_t c = view.indices[q];
+      if (c < 0 || c >= n_time) return false;
+      tq = times[c];
+    }
+    return tq <= t;
+  };
+
+  auto opts = seeds.options();
+  auto nbrs_num = torch::empty({bs}, opts);
+  int64_t* num_ptr = nbrs_num.data_ptr<int64_t>();
+  std::vector<int64_t> offset(bs + 1, 0), pnum(bs, 0);
+  at::parallel_for(0, bs, 64, [&](int64_t start, int64_t end) {
+    for (int64_t i = start; i < end; ++i) {
+      const int64_t v = seed_ptr[i];
+      int64_t p = 0, tq;
+      if (view.degree(v) > 0)
+        for (int64_t q = view.indptr[v]; q < view.indptr[v + 1]; ++q)
+          p += valid(q, st_ptr[i], tq) ? 1 : 0;
+      pnum[i] = p;
+      num_ptr[i] = std::min(kk, p);
+    }
+  });
+  for (int64_t i = 0; i < bs; ++i) offset[i + 1] = offset[i] + num_ptr[i];
+  const int64_t total = offset[bs];
+  auto nbrs = torch::empty({total}, opts);
+  auto out_eids = with_edge ? torch::empty({total}, opts) : torch::Tensor();
+  if (total == 0)
+    return {nbrs, nbrs_num,
+            with_edge ? c10::optional<torch::Tensor>(out_eids)
+                      : c10::nullopt};
+  int64_t* nbrs_ptr = nbrs.data_ptr<int64_t>();
+  int64_t* out_eid_ptr = with_edge ? out_eids.data_ptr<int64_t>() : nullptr;
+  const uint64_t call_seed =
+      last ? 0 : SeedManager::instance().next_call_seed();
+
+  at::parallel_for(0, bs, 64, [&](int64_t start, int64_t end) {
+    std::vector<int64_t> pos, pick;
+    std::vector<std::pair<int64_t, int64_t>> keyed;  // (time, position)
+    for (int64_t i = start; i < end; ++i) {
+      const int64_t cnt = num_ptr[i];
+      if (cnt == 0) continue;
+      const int64_t v = seed_ptr[i];
+      const int64_t p = pnum[i];
+      int64_t* out = nbrs_ptr + offset[i];
+      int64_t* oe = with_edge ? out_eid_ptr + offset[i] : nullptr;
+      pos.clear();
+      keyed.clear();
+      for (int64_t q = view.indptr[v]; q < view.indptr[v + 1]; ++q) {
+        int64_t tq;
+        if (!valid(q, st_ptr[i], tq)) continue;
+        if (last)
+          keyed.emplace_back(tq, q);
+        else
+          pos.push_back(q);
+      }
+      if (last) {
+        // greatest (time, position) first
+        std::partial_sort(keyed.begin(), keyed.begin() + cnt, keyed.end(),
+                          std::greater<std::pair<int64_t, int64_t>>());
+        for (int64_t j = 0; j < cnt; ++j) {
+          out[j] = view.indices[keyed[j].second];
+          if (oe) oe[j] = view.eids[keyed[j].second];
+        }
+      } else if (p <= kk) {
+        for (int64_t j = 0; j < p; ++j) {
+          out[j] = view.indices[pos[j]];
+          if (oe) oe[j] = view.eids[pos[j]];
+        }
+      } else {
+        Rng64 rng(splitmix64(call_seed + (uint64_t)i));
+        pick.resize(kk);
+        floyd_sample(rng, p, kk, pick.data());
+        for (int64_t j = 0; j < kk; ++j) {
+          out[j] = view.indices[pos[pick[j]]];
+          if (oe) oe[j] = view.eids[pos[pick[j]]];
+        }
+      }
+    }
+  });
   return {nbrs, nbrs_num,
           with_edge ? c10::optional<torch::Tensor>(out_eids) : c10::nullopt};
 }

@@ -114,6 +114,34 @@ __device__ __forceinline__ uint64_t feistel_perm(uint64_t key64, uint64_t j,
   return x;
 }
 
+// Inverse of feistel_perm: feistel_perm_inv(key, feistel_perm(key, j, n), n)
+// == j.  The six rounds run backwards, (l, r) <- (r ^ F(l), l), with the same
+// round keys; cycle-walking with the inverse until the result is < n inverts
+// the cycle-walked permutation.  Lets a lane that knows an element's rank
+// decide locally which output slot (if any) drew it.
+__device__ __forceinline__ uint64_t feistel_perm_inv(uint64_t key64,
+                                                     uint64_t y, uint64_t n) {
+  uint32_t total_bits = 64 - __clzll((unsigned long long)(n - 1) | 1ull);
+  uint32_t hb = (total_bits + 1) >> 1;
+  if (hb < 1) hb = 1;
+  const uint32_t hmask = (1u << hb) - 1u;
+  const uint32_t k0 = (uint32_t)key64, k1 = (uint32_t)(key64 >> 32);
+  uint64_t x = y;
+  do {
+    uint32_t l = (uint32_t)(x >> hb) & hmask;
+    uint32_t r = (uint32_t)x & hmask;
+#pragma unroll
+    for (int round = 5; round >= 0; --round) {
+      uint32_t nr = l;
+      l = r ^ (feistel_round(l, k0 + round * 0x7F4A7C15u + (round & 1 ? k1 : 0)) &
+               hmask);
+      r = nr;
+    }
+    x = ((uint64_t)l << hb) | r;
+  } while (x >= n);
+  return x;
+}
+
 // Binary search: greatest i such that offsets[i] <= e, offsets ascending of
 // length m+1 (returns row index in [0, m)).
 __device__ __forceinline__ int64_t row_of(const int64_t* __restrict__ offsets,

@@ -379,6 +379,231 @@ __global__ void random_walk_kernel(const int64_t* __restrict__ indptr,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Temporal neighbour sampling — wave-per-seed, time-filtered.
+//
+// Edge position q of row seeds[i] is valid iff time(q) <= seed_time[i]
+// (time(q) = edge_time[q], or node_time[indices[q]]).  The valid edges are a
+// data-dependent, non-contiguous subset of the row, so the lane-per-output
+// Feistel gather above does not apply.  Instead one wave walks the row in
+// 64-edge chunks: a lane holding a valid edge gets its valid rank from the
+// running count plus the popcount of the ballot bits below it, and the
+// INVERSE permutation tells it locally which output slot (if any) drew that
+// rank.  One pass, no atomics, no LDS, no limit on k.  The wave index goes
+// through readfirstlane so indptr, the seed and its time are scalar loads.
+// Up to kTChunks chunks' loads are issued before the first ballot to keep
+// independent misses in flight.
+// ---------------------------------------------------------------------------
+constexpr int kTChunks = 4;
+
+__device__ __forceinline__ int64_t t_wave_uniform(int64_t v) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+  const uint32_t hi =
+      __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// Time of CSR position q (q inside the row).  With the node-time source a
+// neighbour id outside [0, n_time) has no time: ok = false, never valid.
+template <bool kEdgeTime>
+__device__ __forceinline__ int64_t t_time_at(
+    const int64_t* __restrict__ indices, const int64_t* __restrict__ times,
+    int64_t n_time, int64_t q, bool& ok, int64_t& col) {
+  if (kEdgeTime) {
+    ok = true;
+    return times[q];
+  }
+  col = indices[q];
+  ok = col >= 0 && col < n_time;
+  return ok ? times[col] : 0;
+}
+
+template <bool kEdgeTime>
+__global__ __launch_bounds__(kBlock) void temporal_count_kernel(
+    const int64_t* __restrict__ indptr, const int64_t* __restrict__ indices,
+    const int64_t* __restrict__ times, int64_t n_time, int64_t num_rows,
+    const int64_t* __restrict__ seeds, const int64_t* __restrict__ seed_time,
+    int64_t bs, int64_t k, int64_t* __restrict__ valid_num,
+    int64_t* __restrict__ counts) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = t_wave_uniform(
+      (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave);
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  for (int64_t i = wave; i < bs; i += n_waves) {
+    const int64_t v = seeds[i];
+    int64_t p = 0;
+    if (v >= 0 && v < num_rows) {
+      const int64_t t = seed_time[i];
+      const int64_t base = indptr[v], end = indptr[v + 1];
+      for (int64_t c0 = base; c0 < end; c0 += kTChunks * kWave) {
+        bool ok[kTChunks];
+#pragma unroll
+        for (int u = 0; u < kTChunks; ++u) {
+          const int64_t q = c0 + u * kWave + lane;
+          ok[u] = false;
+          if (q < end) {
+            bool has;
+            int64_t col;
+            const int64_t tq =
+                t_time_at<kEdgeTime>(indices, times, n_time, q, has, col);
+            ok[u] = has && tq <= t;
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < kTChunks; ++u) p += __popcll(__ballot(ok[u]));
+      }
+    }
+    if (lane == 0) {
+      valid_num[i] = p;
+      counts[i] = p < k ? p : k;
+    }
+  }
+}
+
+template <bool kEdgeTime, bool kWithEid>
+__global__ __launch_bounds__(kBlock) void temporal_select_kernel(
+    const int64_t* __restrict__ indptr, const int64_t* __restrict__ indices,
+    const int64_t* __restrict__ eids, const int64_t* __restrict__ times,
+    int64_t n_time, int64_t num_rows, const int64_t* __restrict__ seeds,
+    const int64_t* __restrict__ seed_time, int64_t bs, int64_t k,
+    const int64_t* __restrict__ valid_num,
+    const int64_t* __restrict__ offsets, uint64_t call_seed,
+    int64_t* __restrict__ out_nbrs, int64_t* __restrict__ out_eids) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const uint64_t below = (1ull << lane) - 1ull;
+  const int64_t wave = t_wave_uniform(
+      (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave);
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  for (int64_t i = wave; i < bs; i += n_waves) {
+    const int64_t p = valid_num[i];
+    if (p == 0) continue;  // also covers out-of-range seeds
+    const int64_t v = seeds[i];
+    const int64_t t = seed_time[i];
+    const int64_t base = indptr[v], end = indptr[v + 1];
+    const int64_t off = offsets[i];
+    const bool all = p <= k;
+    const uint64_t key = d_splitmix64(call_seed + (uint64_t)i);
+    int64_t run = 0;
+    for (int64_t c0 = base; c0 < end; c0 += kTChunks * kWave) {
+      bool ok[kTChunks];
+      int64_t col[kTChunks];
+#pragma unroll
+      for (int u = 0; u < kTChunks; ++u) {
+        const int64_t q = c0 + u * kWave + lane;
+        ok[u] = false;
+        col[u] = 0;
+        if (q < end) {
+          bool has;
+          const int64_t tq =
+              t_time_at<kEdgeTime>(indices, times, n_time, q, has, col[u]);
+          ok[u] = has && tq <= t;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kTChunks; ++u) {
+        const uint64_t b = __ballot(ok[u]);
+        if (ok[u]) {
+          const int64_t rank = run + __popcll(b & below);
+          const int64_t j =
+              all ? rank
+                  : (int64_t)feistel_perm_inv(key, (uint64_t)rank,
+                                              (uint64_t)p);
+          if (j < k) {
+            const int64_t q = c0 + u * kWave + lane;
+            out_nbrs[off + j] = kEdgeTime ? indices[q] : col[u];
+            if (kWithEid) out_eids[off + j] = eids[q];
+          }
+        }
+        run += __popcll(b);
+      }
+    }
+  }
+}
+
+// (time, position) arg-max candidate; pos < 0 means none.
+struct TLast {
+  int64_t t;
+  int64_t pos;
+};
+
+__device__ __forceinline__ bool t_after(const TLast& a, const TLast& b) {
+  // a comes after b in "(time, row position) ascending" order
+  return a.t > b.t || (a.t == b.t && a.pos > b.pos);
+}
+
+__device__ __forceinline__ TLast t_wave_argmax(TLast best) {
+#pragma unroll
+  for (int sft = kWave / 2; sft > 0; sft >>= 1) {
+    TLast o;
+    o.t = __shfl_xor(best.t, sft);
+    o.pos = __shfl_xor(best.pos, sft);
+    if (o.pos >= 0 && (best.pos < 0 || t_after(o, best))) best = o;
+  }
+  return best;  // identical in all lanes
+}
+
+// strategy='last': count[i] rounds of a wave arg-max over the valid edges
+// strictly below the previous winner in (time, position) order, emitted
+// greatest first.  Rows of degree <= 64 keep one edge per lane in registers;
+// longer rows re-walk the chunks every round (O(count * deg / 64) per wave).
+template <bool kEdgeTime, bool kWithEid>
+__global__ __launch_bounds__(kBlock) void temporal_last_kernel(
+    const int64_t* __restrict__ indptr, const int64_t* __restrict__ indices,
+    const int64_t* __restrict__ eids, const int64_t* __restrict__ times,
+    int64_t n_time, int64_t num_rows, const int64_t* __restrict__ seeds,
+    const int64_t* __restrict__ seed_time, int64_t bs,
+    const int64_t* __restrict__ counts, const int64_t* __restrict__ offsets,
+    int64_t* __restrict__ out_nbrs, int64_t* __restrict__ out_eids) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = t_wave_uniform(
+      (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave);
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  for (int64_t i = wave; i < bs; i += n_waves) {
+    const int64_t cnt = counts[i];
+    if (cnt == 0) continue;  // also covers out-of-range seeds
+    const int64_t v = seeds[i];
+    const int64_t t = seed_time[i];
+    const int64_t base = indptr[v], end = indptr[v + 1];
+    const int64_t off = offsets[i];
+    const bool small = end - base <= kWave;
+    TLast mine{0, -1};  // small rows: this lane's edge, if valid
+    if (small && base + lane < end) {
+      bool has;
+      int64_t col;
+      const int64_t tq = t_time_at<kEdgeTime>(indices, times, n_time,
+                                              base + lane, has, col);
+      if (has && tq <= t) mine = TLast{tq, base + lane};
+    }
+    TLast prev{0, -1};  // pos < 0: no winner yet, everything is below
+    for (int64_t round = 0; round < cnt; ++round) {
+      TLast best{0, -1};
+      if (small) {
+        if (mine.pos >= 0 && (prev.pos < 0 || t_after(prev, mine)))
+          best = mine;
+      } else {
+        for (int64_t q = base + lane; q < end; q += kWave) {
+          bool has;
+          int64_t col;
+          const int64_t tq =
+              t_time_at<kEdgeTime>(indices, times, n_time, q, has, col);
+          const TLast c{tq, q};
+          if (has && tq <= t && (prev.pos < 0 || t_after(prev, c)) &&
+              (best.pos < 0 || t_after(c, best)))
+            best = c;
+        }
+      }
+      best = t_wave_argmax(best);
+      // cnt <= number of valid edges, so every round finds a winner
+      if (best.pos < 0) break;
+      if (lane == 0) {
+        out_nbrs[off + round] = indices[best.pos];
+        if (kWithEid) out_eids[off + round] = eids[best.pos];
+      }
+      prev = best;
+    }
+  }
+}
+
 uint64_t fresh_seed() { return SeedManager::instance().next_call_seed(); }
 
 }  // namespace
@@ -521,6 +746,105 @@ hip_sample_neighbors(const torch::Tensor& indptr, const torch::Tensor& indices,
       indptr, indices, edge_ids, edge_weights, seeds, k, offsets, total,
       with_edge, weighted, replace);
   return {nbrs, counts, out_eids};
+}
+
+// Temporal one-hop sample: (nbrs, nbrs_num, eids?) in the layout of
+// hip_sample_neighbors.  strategy 'uniform' (last = false) or 'last'.
+std::tuple<torch::Tensor, torch::Tensor, c10::optional<torch::Tensor>>
+hip_sample_neighbors_temporal(const torch::Tensor& indptr,
+                              const torch::Tensor& indices,
+                              const c10::optional<torch::Tensor>& edge_ids,
+                              const torch::Tensor& seeds,
+                              const torch::Tensor& seed_time,
+                              const c10::optional<torch::Tensor>& edge_time,
+                              const c10::optional<torch::Tensor>& node_time,
+                              int64_t k, bool with_edge, bool last) {
+  check_temporal_args(indptr, indices, edge_ids, seeds, seed_time, edge_time,
+                      node_time, with_edge);
+  TORCH_CHECK(indptr.is_cuda(),
+              "hip_sample_neighbors_temporal: tensors must be on GPU (or "
+              "mapped views)");
+  const int64_t num_rows = indptr.size(0) - 1;
+  const int64_t bs = seeds.size(0);
+  const int64_t kk = k < 0 ? std::numeric_limits<int64_t>::max() : k;
+  const bool by_edge = edge_time.has_value();
+  const torch::Tensor& times = by_edge ? *edge_time : *node_time;
+  const int64_t n_time = times.numel();
+  auto opts = seeds.options();
+  auto empty_result = [&](const torch::Tensor& counts) {
+    return std::make_tuple(
+        torch::empty({0}, opts), counts,
+        with_edge ? c10::optional<torch::Tensor>(torch::empty({0}, opts))
+                  : c10::nullopt);
+  };
+  if (bs == 0) return empty_result(torch::empty({0}, opts));
+
+  auto stream = current_stream();
+  const int64_t wv_blocks = std::max<int64_t>(
+      std::min<int64_t>((bs * kWave + kBlock - 1) / kBlock, kMaxBlocks), 1);
+  const dim3 grid((uint32_t)wv_blocks), block(kBlock);
+  auto valid_num = torch::empty({bs}, opts);
+  auto counts = torch::empty({bs}, opts);
+  auto count = [&](auto edge_tag) {
+    constexpr bool ET = decltype(edge_tag)::value;
+    hipLaunchKernelGGL(
+        (temporal_count_kernel<ET>), grid, block, 0, stream,
+        indptr.data_ptr<int64_t>(), indices.data_ptr<int64_t>(),
+        times.data_ptr<int64_t>(), n_time, num_rows,
+        seeds.data_ptr<int64_t>(), seed_time.data_ptr<int64_t>(), bs, kk,
+        valid_num.data_ptr<int64_t>(), counts.data_ptr<int64_t>());
+  };
+  if (by_edge)
+    count(std::true_type{});
+  else
+    count(std::false_type{});
+  auto offsets = torch::zeros({bs + 1}, opts);
+  {
+    auto v = offsets.narrow(0, 1, bs);
+    torch::cumsum_out(v, counts, 0);
+  }
+  const int64_t total = offsets[bs].item<int64_t>();  // hop sync
+  if (total == 0) return empty_result(counts);
+
+  auto nbrs = torch::empty({total}, opts);
+  auto out_eids = with_edge ? torch::empty({total}, opts) : torch::Tensor();
+  const uint64_t cs = last ? 0 : fresh_seed();
+  auto launch = [&](auto edge_tag, auto eid_tag) {
+    constexpr bool ET = decltype(edge_tag)::value;
+    constexpr bool WE = decltype(eid_tag)::value;
+    const int64_t* eid_p = WE ? edge_ids->data_ptr<int64_t>() : nullptr;
+    int64_t* oe_p = WE ? out_eids.data_ptr<int64_t>() : nullptr;
+    if (last) {
+      hipLaunchKernelGGL(
+          (temporal_last_kernel<ET, WE>), grid, block, 0, stream,
+          indptr.data_ptr<int64_t>(), indices.data_ptr<int64_t>(), eid_p,
+          times.data_ptr<int64_t>(), n_time, num_rows,
+          seeds.data_ptr<int64_t>(), seed_time.data_ptr<int64_t>(), bs,
+          counts.data_ptr<int64_t>(), offsets.data_ptr<int64_t>(),
+          nbrs.data_ptr<int64_t>(), oe_p);
+    } else {
+      hipLaunchKernelGGL(
+          (temporal_select_kernel<ET, WE>), grid, block, 0, stream,
+          indptr.data_ptr<int64_t>(), indices.data_ptr<int64_t>(), eid_p,
+          times.data_ptr<int64_t>(), n_time, num_rows,
+          seeds.data_ptr<int64_t>(), seed_time.data_ptr<int64_t>(), bs, kk,
+          valid_num.data_ptr<int64_t>(), offsets.data_ptr<int64_t>(), cs,
+          nbrs.data_ptr<int64_t>(), oe_p);
+    }
+  };
+  if (by_edge) {
+    if (with_edge)
+      launch(std::true_type{}, std::true_type{});
+    else
+      launch(std::true_type{}, std::false_type{});
+  } else {
+    if (with_edge)
+      launch(std::false_type{}, std::true_type{});
+    else
+      launch(std::false_type{}, std::false_type{});
+  }
+  return {nbrs, counts,
+          with_edge ? c10::optional<torch::Tensor>(out_eids) : c10::nullopt};
 }
 
 torch::Tensor hip_lookup_degree(const torch::Tensor& indptr,

@@ -14,6 +14,15 @@ cpu_sample_neighbors(const torch::Tensor& indptr, const torch::Tensor& indices,
                      const c10::optional<torch::Tensor>& edge_weights,
                      const torch::Tensor& seeds, int64_t k, bool with_edge,
                      bool weighted, bool replace = true);
+std::tuple<torch::Tensor, torch::Tensor, c10::optional<torch::Tensor>>
+cpu_sample_neighbors_temporal(const torch::Tensor& indptr,
+                              const torch::Tensor& indices,
+                              const c10::optional<torch::Tensor>& edge_ids,
+                              const torch::Tensor& seeds,
+                              const torch::Tensor& seed_time,
+                              const c10::optional<torch::Tensor>& edge_time,
+                              const c10::optional<torch::Tensor>& node_time,
+                              int64_t k, bool with_edge, bool last);
 torch::Tensor cpu_lookup_degree(const torch::Tensor& indptr,
                                 const torch::Tensor& nodes);
 torch::Tensor cpu_cal_nbr_prob(const torch::Tensor& indptr,

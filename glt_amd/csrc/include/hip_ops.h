@@ -33,6 +33,17 @@ hip_sample_neighbors_gather(const torch::Tensor& indptr,
                             const torch::Tensor& seeds, int64_t k,
                             const torch::Tensor& offsets, int64_t total,
                             bool with_edge, bool weighted, bool replace);
+// Temporal one-hop sample: only edges with time <= seed_time[i] are
+// candidates; exactly one of edge_time [E] / node_time [N] is given.
+std::tuple<torch::Tensor, torch::Tensor, c10::optional<torch::Tensor>>
+hip_sample_neighbors_temporal(const torch::Tensor& indptr,
+                              const torch::Tensor& indices,
+                              const c10::optional<torch::Tensor>& edge_ids,
+                              const torch::Tensor& seeds,
+                              const torch::Tensor& seed_time,
+                              const c10::optional<torch::Tensor>& edge_time,
+                              const c10::optional<torch::Tensor>& node_time,
+                              int64_t k, bool with_edge, bool last);
 torch::Tensor hip_lookup_degree(const torch::Tensor& indptr,
                                 const torch::Tensor& nodes);
 torch::Tensor hip_sample_negative(const torch::Tensor& indptr,

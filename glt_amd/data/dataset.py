@@ -26,15 +26,23 @@ class Dataset:
         self.train_idx = None
         self.val_idx = None
         self.test_idx = None
+        self.node_time: Optional[torch.Tensor] = None
 
     # -- builders -----------------------------------------------------------
     def init_graph(self, edge_index=None, edge_ids=None, edge_weights=None,
                    layout: str = "COO", graph_mode: str = "ZERO_COPY",
                    device: Optional[int] = None,
-                   num_nodes: Optional[int] = None):
-        """edge_index: [2, E] (homo) or Dict[EdgeType, [2, E]] (hetero)."""
+                   num_nodes: Optional[int] = None,
+                   edge_times: Optional[torch.Tensor] = None):
+        """edge_index: [2, E] (homo) or Dict[EdgeType, [2, E]] (hetero).
+        edge_times: optional [E] int64 edge timestamps for temporal
+        sampling (homogeneous graphs only)."""
         target = "CSC" if self.edge_dir == "in" else "CSR"
         if isinstance(edge_index, dict):
+            if edge_times is not None:
+                raise NotImplementedError(
+                    "edge_times: temporal sampling supports homogeneous "
+                    "graphs only")
             self.graph = {}
             for etype, ei in edge_index.items():
                 eid = edge_ids.get(etype) if isinstance(edge_ids, dict) else None
@@ -48,7 +56,7 @@ class Dataset:
         elif edge_index is not None:
             topo = Topology(edge_index, edge_ids, edge_weights,
                             input_layout=layout, layout=target,
-                            num_nodes=num_nodes)
+                            num_nodes=num_nodes, edge_times=edge_times)
             self.graph = Graph(topo, graph_mode, device)
         return self
 
@@ -102,6 +110,21 @@ class Dataset:
     def init_node_labels(self, node_label_data=None):
         if node_label_data is not None:
             self.node_labels = node_label_data
+        return self
+
+    def init_node_times(self, node_time=None):
+        """Per-node int64 timestamps for NeighborLoader(time_attr='node')
+        (homogeneous graphs only)."""
+        if isinstance(node_time, dict) or isinstance(self.graph, dict):
+            raise NotImplementedError(
+                "node times: temporal sampling supports homogeneous "
+                "graphs only")
+        if node_time is not None:
+            node_time = torch.as_tensor(node_time)
+            assert node_time.dim() == 1 and \
+                not node_time.is_floating_point(), \
+                "node_time must be a 1-D integer tensor"
+            self.node_time = node_time.long().contiguous()
         return self
 
     def load_vineyard(self, vineyard_id: str, vineyard_socket: str,
@@ -164,10 +187,13 @@ class Dataset:
             return self.node_labels.get(ntype)
         return self.node_labels
 
+    def get_node_time(self):
+        return self.node_time
+
     # -- process sharing ----------------------------------------------------
     def share_ipc(self):
         for t in (self.node_labels, self.train_idx, self.val_idx,
-                  self.test_idx):
+                  self.test_idx, self.node_time):
             if torch.is_tensor(t) and not t.is_cuda:
                 t.share_memory_()
         if isinstance(self.node_labels, dict):

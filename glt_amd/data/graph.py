@@ -47,31 +47,53 @@ class Topology:
                  edge_weights: Optional[torch.Tensor] = None,
                  input_layout: str = "COO", layout: str = "CSR",
                  num_nodes: Optional[int] = None,
-                 auto_edge_ids: bool = True):
+                 auto_edge_ids: bool = True,
+                 edge_times: Optional[torch.Tensor] = None):
         """auto_edge_ids=False skips materializing the default arange edge
         ids (position ids) — saves 8 bytes/edge when the workload never
-        samples with_edge (e.g. bench.py at papers100M scale)."""
+        samples with_edge (e.g. bench.py at papers100M scale).
+
+        edge_times: optional [E] int64 timestamps aligned with the input
+        edges; carried through every permutation the edge ids go through,
+        so edge_times[q] is the time of edge edge_ids[q]."""
         input_layout = input_layout.upper()
         layout = layout.upper()
         assert layout in ("CSR", "CSC")
         self.layout = layout
+        et = edge_times
+        if et is not None:
+            et = torch.as_tensor(et)
+            assert et.dim() == 1 and not et.is_floating_point(), \
+                "edge_times must be a 1-D integer tensor"
+            et = et.long()
+
+        def convert(fn, a, b, eids, ew, et, **kw):
+            # coo_to_csr / coo_to_csc return a fifth entry only with times
+            out = fn(a, b, eids, ew, edge_time=et, **kw)
+            return out if et is not None else (*out, None)
 
         if input_layout == "COO":
             if torch.is_tensor(edge_index):
                 row, col = edge_index[0], edge_index[1]
             else:
                 row, col = edge_index
+            assert et is None or et.numel() == row.numel(), \
+                "edge_times must have one entry per edge"
             n = num_nodes
             if n is None and row.numel() > 0:
                 n = int(max(int(row.max()), int(col.max()))) + 1
             if layout == "CSR":
-                indptr, indices, eids, ew = coo_to_csr(
-                    row, col, edge_ids, edge_weights, num_rows=n)
+                indptr, indices, eids, ew, et = convert(
+                    coo_to_csr, row, col, edge_ids, edge_weights, et,
+                    num_rows=n)
             else:
-                indptr, indices, eids, ew = coo_to_csc(
-                    row, col, edge_ids, edge_weights, num_cols=n)
+                indptr, indices, eids, ew, et = convert(
+                    coo_to_csc, row, col, edge_ids, edge_weights, et,
+                    num_cols=n)
         elif input_layout in ("CSR", "CSC"):
             indptr, indices = edge_index
+            assert et is None or et.numel() == indices.numel(), \
+                "edge_times must have one entry per edge"
             eids = edge_ids
             if eids is None and (auto_edge_ids or input_layout != layout):
                 eids = torch.arange(indices.numel(), dtype=torch.long,
@@ -84,19 +106,21 @@ class Topology:
                 # input too, not just the COO path
                 from ..utils.topo import sort_csr_indices
 
-                indices, eids, ew = sort_csr_indices(indptr, indices,
-                                                     eids, ew)
+                indices, eids, ew, et = sort_csr_indices(indptr, indices,
+                                                         eids, ew, et)
             if input_layout != layout:
                 # convert via COO round trip
                 num_rows = indptr.numel() - 1
                 rows = torch.repeat_interleave(
                     torch.arange(num_rows), indptr[1:] - indptr[:-1])
                 if layout == "CSC":
-                    indptr, indices, eids, ew = coo_to_csc(
-                        rows, indices, eids, ew, num_cols=num_nodes or num_rows)
+                    indptr, indices, eids, ew, et = convert(
+                        coo_to_csc, rows, indices, eids, ew, et,
+                        num_cols=num_nodes or num_rows)
                 else:
-                    indptr, indices, eids, ew = coo_to_csr(
-                        indices, rows, eids, ew, num_rows=num_nodes or num_rows)
+                    indptr, indices, eids, ew, et = convert(
+                        coo_to_csr, indices, rows, eids, ew, et,
+                        num_rows=num_nodes or num_rows)
         else:
             raise ValueError(f"unknown input_layout {input_layout}")
 
@@ -105,6 +129,7 @@ class Topology:
         self.edge_ids = eids.long().contiguous() if eids is not None else None
         self.edge_weights = (ew.float().contiguous()
                              if ew is not None else None)
+        self.edge_times = et.contiguous() if et is not None else None
 
     @property
     def num_nodes(self) -> int:
@@ -126,7 +151,7 @@ class Topology:
 
     def share_memory_(self):
         for t in (self.indptr, self.indices, self.edge_ids,
-                  self.edge_weights):
+                  self.edge_weights, getattr(self, "edge_times", None)):
             if t is not None and not t.is_cuda:
                 t.share_memory_()
         return self
@@ -155,6 +180,7 @@ class Graph:
         self._indices = None
         self._edge_ids = None
         self._edge_weights = None
+        self._edge_times = None
         self._lazy_done = False
 
     # -- device materialization -------------------------------------------
@@ -162,11 +188,14 @@ class Graph:
         if self._lazy_done:
             return
         topo = self.topo
+        # topologies assembled field by field may predate edge_times
+        topo_times = getattr(topo, "edge_times", None)
         if self.mode == "CPU" or not torch.cuda.is_available():
             self._indptr = topo.indptr
             self._indices = topo.indices
             self._edge_ids = topo.edge_ids
             self._edge_weights = topo.edge_weights
+            self._edge_times = topo_times
         elif self.mode == "CUDA":
             dev = torch.device("cuda",
                                self.device if self.device is not None else
@@ -177,6 +206,8 @@ class Graph:
                               if topo.edge_ids is not None else None)
             self._edge_weights = (topo.edge_weights.to(dev)
                                   if topo.edge_weights is not None else None)
+            self._edge_times = (topo_times.to(dev)
+                                if topo_times is not None else None)
         elif self.mode == "ZERO_COPY":
             from .. import _C
 
@@ -193,6 +224,7 @@ class Graph:
             self._indices = mapped(topo.indices)
             self._edge_ids = mapped(topo.edge_ids)
             self._edge_weights = mapped(topo.edge_weights)
+            self._edge_times = mapped(topo_times)
         else:
             raise ValueError(f"unknown graph mode {self.mode}")
         self._lazy_done = True
@@ -218,6 +250,13 @@ class Graph:
         return self._edge_weights
 
     @property
+    def edge_times(self):
+        """[E] int64 edge timestamps aligned with CSR positions (None when
+        the topology has none); lives where the rest of the CSR lives."""
+        self.lazy_init()
+        return self._edge_times
+
+    @property
     def num_nodes(self):
         return self.topo.num_nodes
 
@@ -240,7 +279,7 @@ class Graph:
         if self._lazy_done and self.mode == "CUDA" and \
                 self._indptr is not None and self._indptr.is_cuda:
             dev_tensors = (self._indptr, self._indices, self._edge_ids,
-                           self._edge_weights)
+                           self._edge_weights, self._edge_times)
         return (self.topo, self.mode, self.device, dev_tensors)
 
     @classmethod
@@ -249,7 +288,7 @@ class Graph:
         g = cls(topo, mode, device)
         if dev_tensors is not None:
             (g._indptr, g._indices, g._edge_ids,
-             g._edge_weights) = dev_tensors
+             g._edge_weights, g._edge_times) = dev_tensors
             g._lazy_done = True
         return g
 

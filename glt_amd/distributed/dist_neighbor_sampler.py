@@ -68,8 +68,12 @@ class DistNeighborSampler:
                  concurrency: int = 4,
                  channel: Optional[ChannelBase] = None,
                  use_all2all: bool = False,
-                 all2all_group=None):
-        """use_all2all: collect remote feature rows with
+                 all2all_group=None,
+                 time_attr: Optional[str] = None):
+        """time_attr: temporal sampling is not implemented across
+        partitions; anything but None raises NotImplementedError.
+
+        use_all2all: collect remote feature rows with
         torch.distributed.all_to_all_single (RCCL over xGMI intra-node)
         instead of per-partition RPC pulls.  Requires one rank per
         partition (of `all2all_group`, default group) stepping in
@@ -79,6 +83,10 @@ class DistNeighborSampler:
         enforce lockstep with a per-epoch batch-count handshake:
         `set_all2all_budget(n)` caps the number of collective batches;
         the ragged tail falls back to the RPC pull path."""
+        if time_attr is not None:
+            raise NotImplementedError(
+                "time_attr: temporal sampling is not implemented for the "
+                "distributed samplers")
         self.data = data
         self.use_all2all = use_all2all
         self.all2all_group = all2all_group

@@ -17,16 +17,38 @@ class NeighborLoader(NodeLoader):
                  device: Optional[torch.device] = None,
                  to_device: Optional[torch.device] = None,
                  edge_dir: Optional[str] = None, seed: Optional[int] = None,
-                 as_pyg_v1: bool = False, prefetch: int = 0, **kwargs):
+                 as_pyg_v1: bool = False, prefetch: int = 0,
+                 time_attr: Optional[str] = None,
+                 input_time: Optional[torch.Tensor] = None,
+                 temporal_strategy: str = "uniform", **kwargs):
+        """time_attr: None, 'node' (times from data.init_node_times) or
+        'edge' (times from init_graph(edge_times=)): a seed observed at
+        input_time[i] only sees neighbours with time <= input_time[i].
+        input_time defaults to the seeds' own node time with 'node' and is
+        required with 'edge'.  temporal_strategy: 'uniform' or 'last'."""
         edge_dir = edge_dir or data.edge_dir
+        if time_attr is None and input_time is not None:
+            raise ValueError("input_time needs time_attr")
         sampler = NeighborSampler(
             data.get_graph() if not isinstance(data.graph, dict)
             else data.graph,
             num_neighbors=num_neighbors, device=device, with_edge=with_edge,
-            with_weight=with_weight, edge_dir=edge_dir, seed=seed)
+            with_weight=with_weight, edge_dir=edge_dir, seed=seed,
+            time_attr=time_attr,
+            node_time=(data.get_node_time() if time_attr == "node"
+                       else None),
+            temporal_strategy=temporal_strategy)
         self.as_pyg_v1 = as_pyg_v1
         super().__init__(data, sampler, input_nodes, batch_size, shuffle,
                          drop_last, with_edge, to_device, prefetch)
+        if input_time is not None:
+            input_time = torch.as_tensor(input_time).long()
+            if input_time.numel() != self.input_nodes.node.numel():
+                raise ValueError(
+                    "input_time must have one entry per input node")
+            self.input_nodes.time = input_time
+        elif time_attr == "edge" and self.input_nodes.time is None:
+            raise ValueError("time_attr='edge' needs input_time")
 
     def __next__(self):
         data = super().__next__()

@@ -17,11 +17,18 @@ from .transform import to_data, to_hetero_data
 
 class _SeedIterator:
     def __init__(self, seeds: torch.Tensor, batch_size: int, shuffle: bool,
-                 drop_last: bool, generator=None):
+                 drop_last: bool, generator=None,
+                 time: Optional[torch.Tensor] = None):
+        """With `time` (one entry per seed) every batch is a
+        (seeds, time) pair; shuffling applies ONE permutation to both."""
         self.batch_size = batch_size
         self.drop_last = drop_last
         n = seeds.numel()
-        if shuffle:
+        if shuffle and time is not None:
+            perm = torch.randperm(n, generator=generator)
+            seeds = seeds[perm.to(seeds.device)]
+            time = time[perm.to(time.device)]
+        elif shuffle:
             # materialize the permutation once: batches become
             # contiguous SLICES, which stay pinned when the seed tensor
             # is pinned (per-batch fancy indexing would return unpinned
@@ -34,6 +41,7 @@ class _SeedIterator:
                 except RuntimeError:
                     pass
         self.seeds = seeds
+        self.time = time
         self.order = None
         self.pos = 0
         self.n = n
@@ -51,6 +59,8 @@ class _SeedIterator:
         batch = (self.seeds[self.order[idx]] if self.order is not None
                  else self.seeds[idx])
         self.pos = end
+        if self.time is not None:
+            return batch, self.time[idx]
         return batch
 
     def __len__(self):
@@ -168,7 +178,8 @@ class NodeLoader:
 
     def __iter__(self):
         self._it = _SeedIterator(self.input_nodes.node, self.batch_size,
-                                 self.shuffle, self.drop_last)
+                                 self.shuffle, self.drop_last,
+                                 time=self.input_nodes.time)
         if self._prefetcher is not None:
             self._prefetcher.stop()
             self._prefetcher = None
@@ -181,7 +192,10 @@ class NodeLoader:
                                  False, self.drop_last))
 
     def _produce(self, seeds):
-        inp = NodeSamplerInput(seeds, self.input_nodes.input_type)
+        time = None
+        if isinstance(seeds, tuple):  # temporal: (seeds, seed times)
+            seeds, time = seeds
+        inp = NodeSamplerInput(seeds, self.input_nodes.input_type, time)
         out = self.sampler.sample_from_nodes(inp)
         with trace_region("collate"):
             return self._collate_fn(out)

@@ -31,19 +31,27 @@ class EdgeIndex(NamedTuple):
 class NodeSamplerInput:
     node: torch.Tensor
     input_type: Optional[NodeType] = None
+    # per-seed time bound for temporal sampling (int64, one per seed)
+    time: Optional[torch.Tensor] = None
 
     def __getitem__(self, index) -> "NodeSamplerInput":
-        return NodeSamplerInput(self.node[index], self.input_type)
+        return NodeSamplerInput(
+            self.node[index], self.input_type,
+            self.time[index] if self.time is not None else None)
 
     def __len__(self):
         return self.node.numel()
 
     def share_memory(self):
         self.node.share_memory_()
+        if self.time is not None:
+            self.time.share_memory_()
         return self
 
     def to(self, device):
-        return NodeSamplerInput(self.node.to(device), self.input_type)
+        return NodeSamplerInput(
+            self.node.to(device), self.input_type,
+            self.time.to(device) if self.time is not None else None)
 
     @classmethod
     def cast(cls, x):

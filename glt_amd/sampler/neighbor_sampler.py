@@ -126,7 +126,16 @@ class NeighborSampler(BaseSampler):
                  with_edge: bool = False, with_neg: bool = False,
                  with_weight: bool = False, edge_dir: str = "out",
                  seed: Optional[int] = None,
-                 weight_replace: bool = True):
+                 weight_replace: bool = True,
+                 time_attr: Optional[str] = None,
+                 node_time: Optional[torch.Tensor] = None,
+                 temporal_strategy: str = "uniform"):
+        """time_attr: None, 'node' or 'edge' — temporal sampling: a seed
+        observed at time t only sees neighbours with time <= t, the time
+        being node_time[neighbour] ('node') or the graph's edge_times
+        ('edge').  temporal_strategy: 'uniform' or 'last' (most recent
+        first).  Temporal sampling is disjoint: every seed slot grows its
+        own tree (see _temporal_sample_from_nodes)."""
         from .. import _C
 
         self._C = _C
@@ -168,6 +177,51 @@ class NeighborSampler(BaseSampler):
         self._deferred_with_eid = (self.with_edge
                                    and g0.edge_ids is not None
                                    if not self.is_hetero else False)
+        self.time_attr = time_attr
+        self.temporal_strategy = temporal_strategy
+        self.node_time = None
+        if time_attr is not None:
+            self._init_temporal(g0, node_time)
+
+    def _init_temporal(self, g0, node_time):
+        if self.time_attr not in ("node", "edge"):
+            raise ValueError(
+                f"time_attr must be None, 'node' or 'edge', got "
+                f"{self.time_attr!r}")
+        if self.temporal_strategy not in ("uniform", "last"):
+            raise ValueError(
+                f"temporal_strategy must be 'uniform' or 'last', got "
+                f"{self.temporal_strategy!r}")
+        if self.is_hetero:
+            raise NotImplementedError(
+                "time_attr: temporal sampling on heterogeneous graphs is "
+                "not implemented")
+        if self.with_weight:
+            raise NotImplementedError(
+                "time_attr: weighted temporal draws are not implemented "
+                "(with_weight=True)")
+        if self.time_attr == "edge":
+            if g0.edge_times is None:
+                raise ValueError(
+                    "time_attr='edge' needs a graph built with edge_times")
+        else:
+            if node_time is None:
+                raise ValueError("time_attr='node' needs node_time")
+            node_time = torch.as_tensor(node_time)
+            if node_time.dim() != 1 or node_time.is_floating_point():
+                raise ValueError("node_time must be a 1-D integer tensor")
+            if node_time.numel() < g0.num_nodes:
+                raise ValueError("node_time must cover every node")
+            self.node_time = node_time.long().contiguous().to(
+                self._sample_device)
+        self.use_deferred = False  # the deferred kernels know no times
+        # Composite-key modulus of the disjoint bookkeeping: greater than
+        # every row and every id in indices.
+        idx = g0.topo.indices
+        self._temporal_mod = max(
+            int(g0.num_nodes),
+            int(idx.max()) + 1 if idx.numel() else 0,
+            self.node_time.numel() if self.node_time is not None else 0, 1)
 
     # ------------------------------------------------------------------
     def _make_inducer(self):
@@ -266,9 +320,96 @@ class NeighborSampler(BaseSampler):
         if self.is_hetero:
             return self._hetero_sample_from_nodes(inputs)
         seeds = self._seeds_to_device(inputs.node)
+        if self.time_attr is not None:
+            with trace_region("sample_from_nodes_temporal"):
+                return self._temporal_sample_from_nodes(
+                    seeds, self._seed_times(seeds, inputs.time),
+                    metadata={"input_type": None})
         with trace_region("sample_from_nodes"):
             return self._sample_from_nodes(seeds,
                                            metadata={"input_type": None})
+
+    # -- temporal (disjoint) ---------------------------------------------
+    def _seed_times(self, seeds: torch.Tensor,
+                    time: Optional[torch.Tensor]) -> torch.Tensor:
+        if time is None:
+            if self.time_attr != "node":
+                raise ValueError(
+                    "time_attr='edge' needs seed times (input_time= / "
+                    "NodeSamplerInput.time)")
+            return self.node_time[seeds]  # PyG: the seeds' own time
+        time = torch.as_tensor(time)
+        if time.numel() != seeds.numel():
+            raise ValueError("seed times must have one entry per seed")
+        return time.long().to(self._sample_device,
+                              non_blocking=True).contiguous()
+
+    def sample_one_hop_temporal(self, srcs: torch.Tensor,
+                                src_time: torch.Tensor,
+                                k: int) -> NeighborOutput:
+        """One-hop sample from srcs, slot i seeing only edges with
+        time <= src_time[i]."""
+        g = self.graph
+        by_edge = self.time_attr == "edge"
+        nbrs, num, eids = self._C.sample_neighbors_temporal(
+            g.indptr, g.indices, srcs.contiguous(), src_time.contiguous(),
+            k, edge_ids=g.edge_ids if self.with_edge else None,
+            edge_time=g.edge_times if by_edge else None,
+            node_time=None if by_edge else self.node_time,
+            with_edge=self.with_edge,
+            last=self.temporal_strategy == "last")
+        return NeighborOutput(nbrs, num, eids)
+
+    def _temporal_sample_from_nodes(self, seeds: torch.Tensor,
+                                    seed_time: torch.Tensor,
+                                    metadata=None) -> SamplerOutput:
+        """Disjoint multi-hop sampling: every seed slot grows its own tree
+        and a node's time bound at every hop is the seed time of its slot.
+        Nodes are deduplicated per (slot, node id) by feeding the inducers
+        composite keys slot * M + node id; two equal seeds stay two slots.
+        """
+        dev = self._sample_device
+        bs = seeds.numel()
+        M = self._temporal_mod
+        assert bs * M < 2 ** 63, "batch_size * M overflows the inducer keys"
+        slots = torch.arange(bs, dtype=torch.long, device=dev)
+        inducer = self._acquire_inducer()
+        src_keys = inducer.init_node(slots * M + seeds)  # all distinct
+        src_nodes, src_slots = seeds, slots
+        out_nodes, out_slots = [seeds], [slots]
+        num_nodes, num_edges = [bs], []
+        rows, cols, eids = [], [], []
+        for k in (self.num_neighbors or []):
+            out = self.sample_one_hop_temporal(src_nodes,
+                                               seed_time[src_slots], k)
+            total = out.nbr.numel()
+            slot_of_nbr = torch.repeat_interleave(src_slots, out.nbr_num,
+                                                  output_size=total)
+            new_keys, r, c = inducer.induce_next(
+                src_keys, slot_of_nbr * M + out.nbr, out.nbr_num)
+            src_keys = new_keys
+            src_nodes = new_keys % M
+            src_slots = torch.div(new_keys, M, rounding_mode="floor")
+            out_nodes.append(src_nodes)
+            out_slots.append(src_slots)
+            num_nodes.append(src_nodes.numel())
+            num_edges.append(r.numel())
+            rows.append(r)
+            cols.append(c)
+            if out.edge is not None:
+                eids.append(out.edge)
+        self._release_inducer(inducer)
+        empty = torch.empty(0, dtype=torch.long, device=dev)
+        md = dict(metadata or {})
+        md["seed_index"] = torch.cat(out_slots)
+        md["seed_time"] = seed_time
+        return SamplerOutput(
+            node=torch.cat(out_nodes),
+            row=torch.cat(rows) if rows else empty,
+            col=torch.cat(cols) if cols else empty,
+            edge=torch.cat(eids) if eids else None, batch=seeds,
+            num_sampled_nodes=num_nodes, num_sampled_edges=num_edges,
+            device=self.device, metadata=md)
 
     # -- deferred-sync fast path ---------------------------------------
     def _acquire_deferred(self, bs: int):
@@ -456,6 +597,10 @@ class NeighborSampler(BaseSampler):
     def sample_from_edges(self, inputs: EdgeSamplerInput,
                           **kwargs) -> Union[SamplerOutput,
                                              HeteroSamplerOutput]:
+        if self.time_attr is not None:
+            raise NotImplementedError(
+                "time_attr: temporal link sampling (sample_from_edges) is "
+                "not implemented")
         neg = inputs.neg_sampling
         if self.is_hetero:
             return self._hetero_sample_from_edges(inputs)

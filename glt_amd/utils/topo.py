@@ -17,10 +17,12 @@ def coo_to_csr(
     edge_id: Optional[torch.Tensor] = None,
     edge_weight: Optional[torch.Tensor] = None,
     num_rows: Optional[int] = None,
-) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor],
-           Optional[torch.Tensor]]:
+    edge_time: Optional[torch.Tensor] = None,
+):
     """Returns (indptr, indices, edge_ids, edge_weights) with indices sorted
-    within each row.  edge_id defaults to the input COO edge position."""
+    within each row.  edge_id defaults to the input COO edge position.
+    With edge_time given, the tuple grows a fifth entry: the times carried
+    through the same permutation as the edge ids."""
     assert row.dim() == 1 and col.dim() == 1 and row.numel() == col.numel()
     row = row.long()
     col = col.long()
@@ -40,13 +42,16 @@ def coo_to_csr(
     torch.cumsum(counts, 0, out=indptr[1:])
     eids = edge_id[perm]
     ew = edge_weight[perm] if edge_weight is not None else None
+    if edge_time is not None:
+        return indptr, indices, eids, ew, edge_time[perm]
     return indptr, indices, eids, ew
 
 
 def coo_to_csc(row, col, edge_id=None, edge_weight=None,
-               num_cols: Optional[int] = None):
+               num_cols: Optional[int] = None, edge_time=None):
     """CSC of (row, col) == CSR of the reversed graph."""
-    return coo_to_csr(col, row, edge_id, edge_weight, num_rows=num_cols)
+    return coo_to_csr(col, row, edge_id, edge_weight, num_rows=num_cols,
+                      edge_time=edge_time)
 
 
 def sort_csr_indices(indptr: torch.Tensor, indices: torch.Tensor,
