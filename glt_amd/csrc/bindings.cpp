@@ -301,6 +301,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         return std::make_tuple(p.big, p.z, p.k_per_z);
       },
       py::arg("Kb"), py::arg("M"), py::arg("N"));
+  m.def("gemm_kt_tile_offset", &gemm_kt_tile_offset, py::arg("row"),
+        py::arg("chunk"));
   m.def("mfma_bf16_selftest", &hip_mfma_bf16_selftest);
   m.def("gat_fused_fwd", &hip_gat_fused_fwd);
   m.def("gat_fused_bwd", &hip_gat_fused_bwd);

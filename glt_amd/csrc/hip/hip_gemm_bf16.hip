@@ -21,10 +21,19 @@
  *
  * Fragment layouts (cdna4 §10): 16x16x32_bf16: A lane l holds
  * A[i=l&15][k=(l>>4)*8+e], B lane l holds B[k=(l>>4)*8+e][j=l&15],
- * C/D col=l&15, row=(l>>4)*4+reg.  Both kernels read fragments as
+ * C/D col=l&15, row=(l>>4)*4+reg.  gemm_bt reads fragments as
  * contiguous 16-byte LDS vectors: A and Bt are staged row-major (their
- * K dim is innermost in global memory already), the kt kernel stages
- * transposed during the write pass instead.
+ * K dim is innermost in global memory already).  The kt operands are
+ * K-major in memory instead.  The 64x64 gemm_kt_kernel transposes them
+ * during its LDS write pass (b32 writes of paired k rows) and reads the
+ * same 16-byte vectors.  The 128x128 gemm_kt128_kernel does not
+ * transpose: it stores each 16-byte global load as one 16-byte LDS write
+ * into a swizzled [k][128] image and builds the fragments with the
+ * transposed LDS read ds_read_b64_tr_b16 (two per operand), prefetches
+ * the next K step into registers across the MFMAs, and sums db from the
+ * staged A tile.  Lane (fi, g) still holds k = kk + 8g + 0..7 and the
+ * MFMA order is unchanged, so dW and db are bit-for-bit those of the
+ * transposing kernel it replaces.
  */
 #include <cstdlib>
 
@@ -456,8 +465,89 @@ void gemm_kt_kernel(const __bf16* __restrict__ A,
 // 128x128 / 8-wave variant of gemm_kt: halves the A/B re-read
 // amplification (traffic ∝ tiles-in-other-dim) for the big dW shapes.
 // Waves as 2(m)x4(n), each wave 64x32 = 4x2 16x16 fragments.
+//
+// Both operands are K-major in memory (the reduction index is the row
+// index), so a 64 x 128 K-step tile is staged exactly as it is loaded:
+// 16-byte LDS writes of the 16-byte global loads into a [k][128] image
+// with 256-byte rows, and ds_read_b64_tr_b16 turns 4-row x 16-column
+// blocks of it into MFMA fragments.  No transposing write pass.
 // ---------------------------------------------------------------------------
 constexpr int KBM = 128, KBN = 128;
+constexpr int KT_ROW_BYTES = KBM * 2;          // one k row of the image
+constexpr int KT_TILE_BYTES = GBK * KT_ROW_BYTES;
+static_assert(KBM == KBN, "A and B share one image geometry");
+
+// Byte offset of 16-byte chunk `ch` (0..15) of k row `row` (0..63) in the
+// tile image.  The XOR spreads both the 8-lane groups of a 16-byte store
+// and the two 4-row blocks a 32-lane half reads transposed over all banks;
+// stores and reads go through this one function.
+__host__ __device__ constexpr int kt_tile_off(int row, int ch) {
+  return KT_ROW_BYTES * row +
+         16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
+}
+
+typedef __attribute__((ext_vector_type(4))) short i16x4;
+typedef __attribute__((ext_vector_type(8))) short i16x8;
+
+// 16x16x32 operand fragment for columns 8*c0 .. 8*c0+15 (c0 even) and
+// k rows r0 .. r0+7 of this lane's 16-lane group: lane (fi, g) ends up
+// with column fi, rows r0 + 0..7 in elements 0..7.  Each transposed read
+// takes a 4-row block; lane 4q+p of the group addresses row q, elements
+// 4p .. 4p+3 of the block.  Every lane of the wave must be active here.
+__device__ __forceinline__ bf16x8 kt_frag(const unsigned char* tile, int r0,
+                                          int c0, int lane) {
+  const int q = (lane & 15) >> 2, p = lane & 3;
+  typedef __attribute__((address_space(3))) i16x4* lds_i16x4;
+  const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4)(
+      tile + kt_tile_off(r0 + q, c0 + (p >> 1)) + 8 * (p & 1)));
+  const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4)(
+      tile + kt_tile_off(r0 + 4 + q, c0 + (p >> 1)) + 8 * (p & 1)));
+  return __builtin_bit_cast(
+      bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// This thread's two 16-byte chunks of the K step at k0: rows
+// k0 + s_row + {0, 32}, columns col0 .. col0+7 of X[Kb, ld].  kt_issue
+// only starts the loads, without a branch, so that nothing waits for them
+// before the MFMAs: a row past kz1 reads row kz1-1 and a chunk that is
+// not wholly inside ld reads columns 0..7 instead (both in bounds: the
+// chunk is not empty and ld >= 8 on this path).  kt_finish, at LDS-write
+// time, zeroes what was out of range (the image is zero-padded, never
+// masked) and fetches a chunk that straddles ld element by element;
+// `straddle` is block-uniform and false whenever ld is a multiple of 8.
+__device__ __forceinline__ void kt_issue(const __bf16* __restrict__ X,
+                                         int64_t ld, int64_t col0,
+                                         int64_t k0, int64_t kz1, int s_row,
+                                         bf16x8 (&v)[2]) {
+  const int64_t c = col0 + 7 < ld ? col0 : 0;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int64_t g_k = std::min<int64_t>(k0 + s_row + 32 * h, kz1 - 1);
+    v[h] = *reinterpret_cast<const bf16x8*>(&X[g_k * ld + c]);
+  }
+}
+
+__device__ __forceinline__ void kt_finish(const __bf16* __restrict__ X,
+                                          int64_t ld, int64_t col0,
+                                          int64_t k0, int64_t kz1, int s_row,
+                                          bool straddle, bf16x8 (&v)[2]) {
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int64_t g_k = k0 + s_row + 32 * h;
+    if (!(g_k < kz1 && col0 + 7 < ld)) v[h] = bf16x8{};
+  }
+  if (straddle) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int64_t g_k = k0 + s_row + 32 * h;
+      if (g_k < kz1 && col0 < ld && col0 + 7 >= ld) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (col0 + e < ld) v[h][e] = X[g_k * ld + col0 + e];
+      }
+    }
+  }
+}
 
 template <bool WITH_DB>
 __global__ __launch_bounds__(512)
@@ -467,8 +557,8 @@ void gemm_kt128_kernel(const __bf16* __restrict__ A,
                        float* __restrict__ db,
                        int64_t Kb, int64_t M, int64_t N,
                        int64_t k_per_z, int64_t plane) {
-  __shared__ __bf16 As[KBM][GBK + LDP];   // As[m][k]
-  __shared__ __bf16 Bs[KBN][GBK + LDP];   // Bs[n][k]
+  alignas(16) __shared__ unsigned char As[KT_TILE_BYTES];   // [k][m]
+  alignas(16) __shared__ unsigned char Bs[KT_TILE_BYTES];   // [k][n]
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -483,84 +573,67 @@ void gemm_kt128_kernel(const __bf16* __restrict__ A,
 
   f32x4b acc[4][2] = {};
 
-  // transposing stage: 512 threads = 16 col-groups x 32 k-pairs
-  const int t_k = (tid >> 4) * 2;          // 0..62 step 2
-  const int t_c = (tid & 15) * 8;          // 0..120 step 8
+  // staging: 512 threads = 32 k rows x 16 chunks, two row sets per tile
+  const int s_row = tid >> 4;              // 0..31 (+32)
+  const int s_ch = tid & 15;               // 16-byte chunk of the row
 
-  const int fi = lane & 15;
-  const int fk8 = (lane >> 4) * 8;
+  const int fg8 = (lane >> 4) * 8;         // fragment k base
+
+  // db: thread (m_l, phase) sums rows phase, phase+4, ... of column m_l
+  const int m_l = tid & 127, phase = tid >> 7;
+  const bool do_db = WITH_DB && blockIdx.y == 0;
+  float s = 0.f;
+
+  // the next K step's loads are in flight in registers during the MFMAs
+  const int64_t a_col = block_row + s_ch * 8, b_col = block_col + s_ch * 8;
+  const bool a_straddle = (M & 7) != 0 && block_row + KBM > M;
+  const bool b_straddle = (N & 7) != 0 && block_col + KBN > N;
+  bf16x8 va[2], vb[2];
+  if (kz0 < kz1) {
+    kt_issue(A, M, a_col, kz0, kz1, s_row, va);
+    kt_issue(B, N, b_col, kz0, kz1, s_row, vb);
+  }
 
   for (int64_t k0 = kz0; k0 < kz1; k0 += GBK) {
-    const int64_t g_k = k0 + t_k;
-    {
-      bf16x8 v0 = {}, v1 = {};
-      if (g_k < kz1 && block_row + t_c < M) {
-        const int64_t base = g_k * M + block_row + t_c;
-        if (block_row + t_c + 7 < M) {
-          v0 = *reinterpret_cast<const bf16x8*>(&A[base]);
-          if (g_k + 1 < kz1)
-            v1 = *reinterpret_cast<const bf16x8*>(&A[base + M]);
-        } else {
+    kt_finish(A, M, a_col, k0, kz1, s_row, a_straddle, va);
+    kt_finish(B, N, b_col, k0, kz1, s_row, b_straddle, vb);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            if (block_row + t_c + e < M) {
-              v0[e] = A[base + e];
-              if (g_k + 1 < kz1) v1[e] = A[base + M + e];
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        __bf16 pair[2] = {v0[e], v1[e]};
-        *reinterpret_cast<uint32_t*>(&As[t_c + e][t_k]) =
-            *reinterpret_cast<const uint32_t*>(pair);
-      }
-    }
-    {
-      bf16x8 v0 = {}, v1 = {};
-      if (g_k < kz1 && block_col + t_c < N) {
-        const int64_t base = g_k * N + block_col + t_c;
-        if (block_col + t_c + 7 < N) {
-          v0 = *reinterpret_cast<const bf16x8*>(&B[base]);
-          if (g_k + 1 < kz1)
-            v1 = *reinterpret_cast<const bf16x8*>(&B[base + N]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            if (block_col + t_c + e < N) {
-              v0[e] = B[base + e];
-              if (g_k + 1 < kz1) v1[e] = B[base + N + e];
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        __bf16 pair[2] = {v0[e], v1[e]};
-        *reinterpret_cast<uint32_t*>(&Bs[t_c + e][t_k]) =
-            *reinterpret_cast<const uint32_t*>(pair);
-      }
+    for (int h = 0; h < 2; ++h) {
+      *reinterpret_cast<bf16x8*>(
+          As + kt_tile_off(s_row + 32 * h, s_ch)) = va[h];
+      *reinterpret_cast<bf16x8*>(
+          Bs + kt_tile_off(s_row + 32 * h, s_ch)) = vb[h];
     }
     __syncthreads();
+    if (k0 + GBK < kz1) {
+      kt_issue(A, M, a_col, k0 + GBK, kz1, s_row, va);
+      kt_issue(B, N, b_col, k0 + GBK, kz1, s_row, vb);
+    }
 
 #pragma unroll
     for (int kk = 0; kk < GBK; kk += 32) {
       bf16x8 a[4], b[2];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        a[i] = *reinterpret_cast<const bf16x8*>(
-            &As[wm * 64 + i * 16 + fi][kk + fk8]);
+        a[i] = kt_frag(As, kk + fg8, wm * 8 + i * 2, lane);
 #pragma unroll
       for (int j = 0; j < 2; ++j)
-        b[j] = *reinterpret_cast<const bf16x8*>(
-            &Bs[wn * 32 + j * 16 + fi][kk + fk8]);
+        b[j] = kt_frag(Bs, kk + fg8, wn * 4 + j * 2, lane);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
               a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+    if (do_db) {
+      // from the staged tile, in ascending k; the zero rows past kz1 add
+      // +0 to a sum that is never -0, so the result is that of the
+      // bounded loop
+#pragma unroll
+      for (int r = 0; r < GBK; r += 4)
+        s += bf2f(*reinterpret_cast<const __bf16*>(
+            As + kt_tile_off(r + phase, m_l >> 3) + 2 * (m_l & 7)));
     }
     __syncthreads();
   }
@@ -580,14 +653,8 @@ void gemm_kt128_kernel(const __bf16* __restrict__ A,
       }
     }
   }
-  if (WITH_DB && blockIdx.y == 0) {
+  if (do_db) {
     __shared__ float dbs[KBM][4];
-    const int m_l = tid & 127, phase = tid >> 7;
-    float s = 0.f;
-    if (block_row + m_l < M) {
-      for (int64_t k = kz0 + phase; k < kz1; k += 4)
-        s += bf2f(A[k * M + block_row + m_l]);
-    }
     dbs[m_l][phase] = s;
     __syncthreads();
     if (tid < KBM && block_row + tid < M)
@@ -701,6 +768,15 @@ GemmKtPlan gemm_kt_bf16_plan(int64_t Kb, int64_t M, int64_t N) {
       std::max<int64_t>(GBK, ((Kb + z - 1) / z + GBK - 1) / GBK * GBK);
   p.z = std::max<int64_t>(1, (Kb + p.k_per_z - 1) / p.k_per_z);
   return p;
+}
+
+// Byte offset of 16-byte chunk `chunk` of k row `row` in the 128x128
+// kernel's [64][128] bf16 LDS tile image (the function the kernel stores
+// and reads through; the tests check the layout with it, without a GPU).
+int64_t gemm_kt_tile_offset(int64_t row, int64_t chunk) {
+  TORCH_CHECK(row >= 0 && row < GBK && chunk >= 0 && chunk < KBM / 8,
+              "row in [0, 64) and chunk in [0, 16) required");
+  return kt_tile_off((int)row, (int)chunk);
 }
 
 // (dW, db) = (A^T @ B, colsum(A)): A [Kb,M] bf16, B [Kb,N] bf16;

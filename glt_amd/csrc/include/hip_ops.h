@@ -227,6 +227,8 @@ struct GemmKtPlan {
   int64_t m_t, n_t, z, k_per_z;
 };
 GemmKtPlan gemm_kt_bf16_plan(int64_t Kb, int64_t M, int64_t N);
+// Byte offset of a 16-byte chunk in the 128x128 kernel's LDS tile image.
+int64_t gemm_kt_tile_offset(int64_t row, int64_t chunk);
 torch::Tensor hip_mfma_bf16_selftest(const torch::Tensor& A,
                                      const torch::Tensor& B);
 
