@@ -316,6 +316,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("segment_mean_cat_bwd", &hip_segment_mean_cat_bwd, py::arg("dy"),
         py::arg("col"), py::arg("offsets"), py::arg("n_src"),
         py::arg("order_independent") = false);
+  m.def("segment_transpose", &hip_segment_transpose, py::arg("col"),
+        py::arg("n_src"), py::arg("tgt") = py::none());
+  m.def("segment_mean_bwd_gather", &hip_segment_mean_bwd_gather,
+        py::arg("dy"), py::arg("col"), py::arg("offsets"), py::arg("n_src"),
+        py::arg("order_independent"), py::arg("src_off"), py::arg("in_edge"),
+        py::arg("mask") = py::none());
+  m.def("segment_mean_cat_bwd_gather", &hip_segment_mean_cat_bwd_gather,
+        py::arg("dy"), py::arg("col"), py::arg("offsets"), py::arg("n_src"),
+        py::arg("order_independent"), py::arg("src_off"), py::arg("in_edge"),
+        py::arg("mask") = py::none());
   m.def("segment_wsum_fwd", &hip_segment_wsum_fwd, py::arg("x"),
         py::arg("col"), py::arg("offsets"), py::arg("w") = py::none(),
         py::arg("a") = py::none(), py::arg("b") = py::none());

@@ -2,11 +2,14 @@
  *
  * The glt_amd sampler emits batch edges sorted by target local id, so the
  * per-target segments are contiguous: forward is one wave-per-target kernel
- * (no atomics, fused mean), backward scatters dY/deg into dX with fp32
- * atomics (same contention class as torch index_add_, but fused with the
- * degree division and vectorized).
+ * (no atomics, fused mean).  Backward, two forms: the gather backward
+ * (seg_mean_bwd_gather_kernel, the python layer's default) sums dY/deg per
+ * source row through an inverted index of the edges, without atomics or
+ * an arena; the scatter backward (seg_mean_bwd_kernel) adds dY/deg into
+ * an fp32 arena with atomics (same contention class as torch index_add_,
+ * but fused with the degree division and vectorized).
  *
- * Default backward: plain fp32 atomics, so low-order bits depend on the
+ * Scatter backward: plain fp32 atomics, so low-order bits depend on the
  * order in which they land.  order_independent = true (the python layer
  * passes it in deterministic mode, see glt_amd/ops/segment.py) trades
  * precision for run-to-run reproducibility: every contribution is first
@@ -24,9 +27,10 @@
  *
  * dtype: templated over fp32 and bf16 inputs with fp32 accumulation —
  * the kernels are HBM-bound (see profiles/), so bf16 halves the roofline
- * traffic.  Backward always accumulates into an fp32 arena (bf16 atomics
- * lose too much precision for degree-weighted sums); the python wrapper
- * casts once at the end.
+ * traffic.  The scatter backward always accumulates into an fp32 arena
+ * (bf16 atomics lose too much precision for degree-weighted sums) and the
+ * python wrapper casts once at the end; the gather backward sums in fp32
+ * registers and stores dy's dtype itself.
  *
  * seg_wsum_*: the weighted segment sum behind GCNConv and edge weights
  * (out[t] = a[t] * sum_e w[e] * b[col[e]] * x[col[e]]) with its dx and
@@ -37,6 +41,7 @@
  * one atomic per output element into the same arena.
  */
 #include <hip/hip_bf16.h>
+#include <rocprim/device/device_radix_sort.hpp>
 
 #include "hip_common.h"
 #include "../include/common.h"
@@ -275,6 +280,297 @@ __device__ __forceinline__ int64_t wave_uniform(int64_t v) {
   const uint32_t hi =
       __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
   return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// ---------------------------------------------------------------------------
+// Atomic-free segment-mean backward: gather by source.
+//   dx[s, :] = sum over in-edges (t -> s) of dy[t, :F] / deg(t)
+//              (+ dy[s, F:] if s < n_tgt with kCat)
+// summed in fp32 per SOURCE row through the inverted index of col
+// (src_off / in_tgt, built by hip_segment_transpose), rounded once to dy's
+// dtype and, with kMask, masked by the ReLU of the layer below.  One pass:
+// no arena, no zero fill, no atomics, no separate cast or mask kernel.
+// Every row of dx is stored, also rows nothing contributes to (zeros).
+//
+// The terms, inv, snap and grid_magic are those of seg_mean_bwd_kernel.  In
+// order-independent mode, within the headroom, the fp32 sums are exact in
+// any order, so the result has the bits of the atomic path followed by
+// Tensor.to(dtype) and threshold_backward.  Each in-list keeps the edge
+// order (stable sort), so plain mode is run-to-run identical too, which
+// the atomic path is not.
+//
+// Known limit: one wave sums a source's whole in-list; a hub source with
+// thousands of in-edges serialises on it (list splitting is the follow-up).
+// ---------------------------------------------------------------------------
+
+// src_off[k] = first position i of the sorted keys with key[i] >= k (and
+// n_edge past the last key): position i fills k in (key[i-1], key[i]], the
+// head [0, key[0]] and the tail (key[E-1], n_src] are spread over the grid.
+// No atomics, no cumsum.  Keys outside [0, n_src) break the caller's
+// contract; they are clamped so that no store leaves src_off.
+__global__ void seg_boundary_kernel(const int64_t* __restrict__ key,
+                                    int64_t n_edge, int64_t n_src,
+                                    int64_t* __restrict__ src_off) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t g0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  auto clamped = [n_src](int64_t k) {
+    return k < 0 ? (int64_t)-1 : (k < n_src ? k : n_src - 1);
+  };
+  const int64_t first = clamped(key[0]), last = clamped(key[n_edge - 1]);
+  for (int64_t k = g0; k <= first; k += stride) src_off[k] = 0;
+  for (int64_t k = last + 1 + g0; k <= n_src; k += stride)
+    src_off[k] = n_edge;
+  for (int64_t i = 1 + g0; i < n_edge; i += stride) {
+    const int64_t hi = clamped(key[i]);
+    for (int64_t k = clamped(key[i - 1]) + 1; k <= hi; ++k) src_off[k] = i;
+  }
+}
+
+// A lane's share of one row per pass, as kVals fp32 channels.  Lanes past
+// the row end read the row's last unit and do not store.
+__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
+  // c10's float -> bf16: RNE, as Tensor.to()
+  return (uint32_t)c10::BFloat16(lo).x | ((uint32_t)c10::BFloat16(hi).x << 16);
+}
+
+// bf16, F % 4 == 0: rows are arrays of U = F / 4 units of four channels,
+// one 8-byte load per lane per row visit, 256 channels per pass (a
+// flagship row, F = 256, is one wave instruction).
+struct GatherBf164 {
+  using unit_t = uint2;
+  static constexpr int kVals = 4;
+  static constexpr int kUnitsPerPass = kWave;
+  __device__ static __forceinline__ void load(const unit_t* __restrict__ p,
+                                              int64_t row, int64_t fb,
+                                              int lane, int64_t U,
+                                              float (&v)[kVals]) {
+    const int64_t u = fb + lane;
+    const uint2 w = p[row + (u < U ? u : U - 1)];
+    v[0] = __uint_as_float(w.x << 16);
+    v[1] = __uint_as_float(w.x & 0xffff0000u);
+    v[2] = __uint_as_float(w.y << 16);
+    v[3] = __uint_as_float(w.y & 0xffff0000u);
+  }
+  __device__ static __forceinline__ void store(unit_t* __restrict__ p,
+                                               int64_t row, int64_t fb,
+                                               int lane, int64_t U,
+                                               const float (&v)[kVals]) {
+    const int64_t u = fb + lane;
+    if (u < U) p[row + u] = make_uint2(pack_bf16(v[0], v[1]),
+                                       pack_bf16(v[2], v[3]));
+  }
+};
+
+// bf16, other even F: U = F / 2 channel pairs, one 4-byte load per lane
+// per row visit, 128 channels per pass.
+struct GatherBf162 {
+  using unit_t = uint32_t;
+  static constexpr int kVals = 2;
+  static constexpr int kUnitsPerPass = kWave;
+  __device__ static __forceinline__ void load(const unit_t* __restrict__ p,
+                                              int64_t row, int64_t fb,
+                                              int lane, int64_t U,
+                                              float (&v)[kVals]) {
+    const int64_t u = fb + lane;
+    const uint32_t w = p[row + (u < U ? u : U - 1)];
+    v[0] = __uint_as_float(w << 16);
+    v[1] = __uint_as_float(w & 0xffff0000u);
+  }
+  __device__ static __forceinline__ void store(unit_t* __restrict__ p,
+                                               int64_t row, int64_t fb,
+                                               int lane, int64_t U,
+                                               const float (&v)[kVals]) {
+    const int64_t u = fb + lane;
+    if (u < U) p[row + u] = pack_bf16(v[0], v[1]);
+  }
+};
+
+// fp32, F % 4 == 0: U = F / 4 float4 units, 16 bytes per lane, 256
+// channels per pass.
+struct GatherF324 {
+  using unit_t = float4;
+  static constexpr int kVals = 4;
+  static constexpr int kUnitsPerPass = kWave;
+  __device__ static __forceinline__ void load(const unit_t* __restrict__ p,
+                                              int64_t row, int64_t fb,
+                                              int lane, int64_t U,
+                                              float (&v)[kVals]) {
+    const int64_t u = fb + lane;
+    const float4 w = p[row + (u < U ? u : U - 1)];
+    v[0] = w.x;
+    v[1] = w.y;
+    v[2] = w.z;
+    v[3] = w.w;
+  }
+  __device__ static __forceinline__ void store(unit_t* __restrict__ p,
+                                               int64_t row, int64_t fb,
+                                               int lane, int64_t U,
+                                               const float (&v)[kVals]) {
+    const int64_t u = fb + lane;
+    if (u < U) p[row + u] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+};
+
+// Any other fp32 F, and bf16 with odd F: U = F channels, a lane owns f and
+// f + 64 (128 channels per pass).
+template <typename scalar_t>
+struct GatherScalar {
+  using unit_t = scalar_t;
+  static constexpr int kVals = 2;
+  static constexpr int kUnitsPerPass = 2 * kWave;
+  __device__ static __forceinline__ void load(const unit_t* __restrict__ p,
+                                              int64_t row, int64_t fb,
+                                              int lane, int64_t U,
+                                              float (&v)[kVals]) {
+    const int64_t u0 = fb + lane, u1 = fb + lane + kWave;
+    v[0] = static_cast<float>(p[row + (u0 < U ? u0 : U - 1)]);
+    v[1] = fb + kWave < U  // wave-uniform
+               ? static_cast<float>(p[row + (u1 < U ? u1 : U - 1)])
+               : 0.f;
+  }
+  __device__ static __forceinline__ void store(unit_t* __restrict__ p,
+                                               int64_t row, int64_t fb,
+                                               int lane, int64_t U,
+                                               const float (&v)[kVals]) {
+    const int64_t u0 = fb + lane, u1 = fb + lane + kWave;
+    if (u0 < U) p[row + u0] = static_cast<scalar_t>(v[0]);
+    if (u1 < U) p[row + u1] = static_cast<scalar_t>(v[1]);
+  }
+};
+
+// Target row and 1 / deg of the in-list entry at position k, in scalar
+// registers.  in_tgt holds the TARGET id of each in-edge (not its edge
+// position: that would cost a search of off per edge).  An entry that
+// names no target of this call (t outside [0, n_tgt)) contributes nothing,
+// like an edge past off[n_tgt] on the atomic path.
+__device__ __forceinline__ void gather_entry(const int64_t* __restrict__ in_tgt,
+                                             const int64_t* __restrict__ off,
+                                             int64_t k, int64_t n_tgt,
+                                             int64_t ostride, int64_t& row,
+                                             float& inv, bool& use) {
+  int64_t t = in_tgt[k];
+  use = t >= 0 && t < n_tgt;
+  if (!use) t = 0;
+  const int64_t deg = off[t + 1] - off[t];
+  inv = 1.0f / (float)deg;
+  row = t * ostride;
+}
+
+// List bounds of kRows consecutive sources and the first entry of each
+// list: everything a wave needs before it can issue a block's row loads,
+// all in scalar registers (three dependent scalar loads).
+template <int kRows>
+struct GatherBlock {
+  int64_t lb[kRows + 1];
+  int64_t row0[kRows];
+  float inv0[kRows];
+  bool use0[kRows];
+
+  __device__ __forceinline__ void load(const int64_t* __restrict__ src_off,
+                                       const int64_t* __restrict__ in_tgt,
+                                       const int64_t* __restrict__ off,
+                                       int64_t s0, int64_t n_src,
+                                       int64_t n_tgt, int64_t ostride) {
+    // rows past n_src get an empty list (both bounds src_off[n_src])
+#pragma unroll
+    for (int r = 0; r <= kRows; ++r)
+      lb[r] = src_off[s0 + r < n_src ? s0 + r : n_src];
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+      row0[r] = 0;
+      inv0[r] = 0.f;
+      use0[r] = false;
+      if (lb[r + 1] > lb[r])
+        gather_entry(in_tgt, off, lb[r], n_tgt, ostride, row0[r], inv0[r],
+                     use0[r]);
+    }
+  }
+};
+
+// The mean in-degree of a sampled batch is about 1.1, so there is nothing
+// to batch along a list.  A wave takes kRows consecutive sources, whose
+// list bounds, first in-edges and dy / root / mask row loads are issued
+// together, and while those row loads are in flight it runs the scalar
+// loads of its NEXT block, so the two dependent chains overlap.  Longer
+// lists continue in an inner loop, four entries per batch, added in list
+// order.
+template <typename P, bool kCat, bool kMask, int kRows>
+__global__ void seg_mean_bwd_gather_kernel(
+    const typename P::unit_t* __restrict__ dy, const int64_t* __restrict__ off,
+    const int64_t* __restrict__ src_off, const int64_t* __restrict__ in_tgt,
+    const typename P::unit_t* __restrict__ mask, int64_t n_tgt, int64_t n_src,
+    int64_t U, const float* __restrict__ amax_parts, int n_parts,
+    typename P::unit_t* __restrict__ out) {
+  constexpr int kVals = P::kVals;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = wave_uniform(
+      (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / kWave);
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int64_t ostride = kCat ? 2 * U : U;
+  const int64_t n_blk = (n_src + kRows - 1) / kRows;
+  GatherBlock<kRows> cur = {}, nxt = {};
+  if (wave < n_blk)
+    cur.load(src_off, in_tgt, off, wave * kRows, n_src, n_tgt, ostride);
+  const float magic = grid_magic(amax_parts, n_parts);
+  for (int64_t blk = wave; blk < n_blk; blk += n_waves) {
+    const int64_t s0 = blk * kRows;
+    for (int64_t fb = 0; fb < U; fb += P::kUnitsPerPass) {
+      float root[kRows][kVals], m[kRows][kVals], v[kRows][kVals];
+#pragma unroll
+      for (int r = 0; r < kRows; ++r) {
+        const int64_t s = s0 + r;
+#pragma unroll
+        for (int j = 0; j < kVals; ++j) root[r][j] = m[r][j] = 0.f;
+        if (kCat && s < n_tgt)
+          P::load(dy, s * ostride + U, fb, lane, U, root[r]);
+        if (kMask && s < n_src) P::load(mask, s * U, fb, lane, U, m[r]);
+        P::load(dy, cur.row0[r], fb, lane, U, v[r]);
+      }
+      if (fb == 0 && blk + n_waves < n_blk)
+        nxt.load(src_off, in_tgt, off, (blk + n_waves) * kRows, n_src, n_tgt,
+                 ostride);
+#pragma unroll
+      for (int r = 0; r < kRows; ++r) {
+        const int64_t s = s0 + r;
+        if (s >= n_src) break;
+        float acc[kVals];
+#pragma unroll
+        for (int j = 0; j < kVals; ++j) {
+          acc[j] = 0.f;
+          if (kCat && s < n_tgt) acc[j] += snap(root[r][j], magic);
+          if (cur.use0[r]) acc[j] += snap(v[r][j] * cur.inv0[r], magic);
+        }
+        for (int64_t k0 = cur.lb[r] + 1; k0 < cur.lb[r + 1]; k0 += 4) {
+          const int nb =
+              (int)((cur.lb[r + 1] - k0) < 4 ? (cur.lb[r + 1] - k0) : 4);
+          int64_t row[4];
+          float inv[4];
+          bool use[4];
+          float w[4][kVals];
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            gather_entry(in_tgt, off, q < nb ? k0 + q : k0, n_tgt, ostride,
+                         row[q], inv[q], use[q]);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) P::load(dy, row[q], fb, lane, U, w[q]);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            if (q < nb && use[q]) {  // wave-uniform
+#pragma unroll
+              for (int j = 0; j < kVals; ++j)
+                acc[j] += snap(w[q][j] * inv[q], magic);
+            }
+          }
+        }
+        // threshold_backward's rule: a NaN mask passes, masked gives +0
+#pragma unroll
+        for (int j = 0; j < kVals; ++j)
+          if (kMask && m[r][j] <= 0.f) acc[j] = 0.f;
+        P::store(out, s * U, fb, lane, U, acc);
+      }
+    }
+    cur = nxt;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -850,6 +1146,113 @@ void with_flag(bool v, Fn&& fn) {
     fn(std::false_type{});
 }
 
+// 1-D contiguous int64 index tensor on the device
+void check_index_1d(const torch::Tensor& t, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 1 && t.is_contiguous() &&
+                  t.scalar_type() == torch::kInt64,
+              "segment: ", what, " must be a contiguous 1-D int64 tensor on "
+              "device");
+}
+
+// consecutive sources per wave of the gather backward: 1, 2, 4 and 8 were
+// measured at the flagship shapes and 1 was fastest (docs/kernels.md)
+constexpr int kGatherRows = 1;
+
+template <typename P, bool kCat, int kRows>
+void segment_mean_bwd_gather_launch(const torch::Tensor& dyc,
+                                    const torch::Tensor& offsets,
+                                    const torch::Tensor& src_off,
+                                    const torch::Tensor& in_tgt,
+                                    const torch::Tensor* mask, int64_t n_src,
+                                    int64_t units, const float* parts,
+                                    int n_parts, torch::Tensor& out) {
+  using unit_t = typename P::unit_t;
+  const int64_t n_blk = (n_src + kRows - 1) / kRows;
+  with_flag(mask != nullptr, [&](auto kMask) {
+    hipLaunchKernelGGL(
+        (seg_mean_bwd_gather_kernel<P, kCat, decltype(kMask)::value, kRows>),
+        dim3(wave_grid(n_blk)), dim3(kBlock), 0, current_stream(),
+        reinterpret_cast<const unit_t*>(dyc.data_ptr()),
+        offsets.data_ptr<int64_t>(), src_off.data_ptr<int64_t>(),
+        in_tgt.data_ptr<int64_t>(),
+        mask ? reinterpret_cast<const unit_t*>(mask->data_ptr()) : nullptr,
+        dyc.size(0), n_src, units, parts, n_parts,
+        reinterpret_cast<unit_t*>(out.data_ptr()));
+  });
+}
+
+// dx [n_src, F] in dy's dtype, every row written by the kernel
+template <bool kCat>
+torch::Tensor segment_mean_bwd_gather(
+    const torch::Tensor& dy, const torch::Tensor& col,
+    const torch::Tensor& offsets, int64_t n_src, bool order_independent,
+    const torch::Tensor& src_off, const torch::Tensor& in_tgt,
+    const c10::optional<torch::Tensor>& mask) {
+  check_values(dy, "dy", false);
+  const int64_t n_tgt = dy.size(0);
+  check_index(col, offsets, n_tgt);
+  if (kCat) {
+    TORCH_CHECK(dy.size(1) % 2 == 0,
+                "segment_mean_cat: dy must have an even number of columns");
+    TORCH_CHECK(n_src >= n_tgt,
+                "segment_mean_cat: targets must be a row prefix of x");
+  }
+  const int64_t feat = kCat ? dy.size(1) / 2 : dy.size(1);
+  check_index_1d(src_off, "src_off");
+  check_index_1d(in_tgt, "in_edge");
+  TORCH_CHECK(n_src >= 0 && src_off.numel() == n_src + 1 &&
+                  in_tgt.numel() == col.numel(),
+              "segment: src_off must have n_src + 1 entries and in_edge one "
+              "per edge (segment_transpose(col, n_src, tgt))");
+  if (mask.has_value())
+    TORCH_CHECK(mask->is_cuda() && mask->dim() == 2 &&
+                    mask->is_contiguous() && mask->size(0) >= n_src &&
+                    mask->size(1) == feat &&
+                    mask->scalar_type() == dy.scalar_type(),
+                "segment: mask must be a contiguous [>= n_src, F] tensor of "
+                "dy's dtype on device");
+  if (n_tgt == 0 || feat == 0 || n_src == 0)
+    return torch::zeros({n_src, feat}, dy.options());
+  auto dyc = dy.contiguous();
+  auto out = torch::empty({n_src, feat}, dy.options());
+  const torch::Tensor* mp = mask.has_value() ? &*mask : nullptr;
+  torch::Tensor parts_t;  // block maxima of |dy|: the order-independent grid
+  float* parts = nullptr;
+  int n_parts = 0;
+  if (order_independent) {
+    const int64_t n = dyc.numel();
+    n_parts = (int)std::min<int64_t>((n + kZeroBlock - 1) / kZeroBlock,
+                                     kMaxAmaxParts);
+    parts_t = torch::empty({n_parts}, dy.options().dtype(torch::kFloat32));
+    parts = parts_t.data_ptr<float>();
+    GLT_DISPATCH_SEG(dy.scalar_type(), "segment_mean_bwd_gather", [&] {
+      hipLaunchKernelGGL(zero_absmax_kernel<scalar_t>, dim3(n_parts),
+                         dim3(kZeroBlock), 0, current_stream(),
+                         (float*)nullptr, (int64_t)0,
+                         dyc.data_ptr<scalar_t>(), n, parts);
+    });
+  }
+#define GLT_GATHER(P, UNITS)                                          \
+  segment_mean_bwd_gather_launch<P, kCat, kGatherRows>(               \
+      dyc, offsets, src_off, in_tgt, mp, n_src, UNITS, parts, n_parts, out)
+  const bool bf16 = dy.scalar_type() == torch::kBFloat16;
+  // the wide units need their alignment (a view may start anywhere)
+  const uintptr_t addr = (uintptr_t)dyc.data_ptr() | (uintptr_t)out.data_ptr() |
+                         (mp ? (uintptr_t)mp->data_ptr() : 0);
+  if (bf16 && feat % 4 == 0 && addr % 8 == 0)
+    GLT_GATHER(GatherBf164, feat / 4);
+  else if (bf16 && feat % 2 == 0 && addr % 4 == 0)
+    GLT_GATHER(GatherBf162, feat / 2);
+  else if (!bf16 && feat % 4 == 0 && addr % 16 == 0)
+    GLT_GATHER(GatherF324, feat / 4);
+  else if (bf16)
+    GLT_GATHER(GatherScalar<c10::BFloat16>, feat);
+  else
+    GLT_GATHER(GatherScalar<float>, feat);
+#undef GLT_GATHER
+  return out;
+}
+
 template <bool kMax, bool kCat, bool kArg>
 void segment_ext_fwd_launch(const torch::Tensor& x, const torch::Tensor& col,
                             const torch::Tensor& offsets, int64_t n_tgt,
@@ -915,6 +1318,74 @@ torch::Tensor hip_segment_mean_cat_bwd(const torch::Tensor& dy,
                                        int64_t n_src,
                                        bool order_independent) {
   return segment_mean_bwd<true>(dy, col, offsets, n_src, order_independent);
+}
+
+// Inverted index of col: (src_off int64 [n_src + 1], in_edge int64 [E]).
+// in_edge[src_off[s] : src_off[s + 1]] lists the edges e with col[e] == s
+// in ascending e (stable sort): as tgt[e] when tgt is given (what the
+// gather backward reads), as the position e otherwise.  A stable rocprim
+// radix_sort_pairs over the low ceil(log2(n_src)) key bits and one
+// boundary kernel; scratch from the caching allocator, no host sync.
+std::tuple<torch::Tensor, torch::Tensor> hip_segment_transpose(
+    const torch::Tensor& col, int64_t n_src,
+    const c10::optional<torch::Tensor>& tgt) {
+  check_index_1d(col, "col");
+  const int64_t n_edge = col.numel();
+  TORCH_CHECK(n_src >= 0, "segment_transpose: n_src must be >= 0");
+  if (tgt.has_value()) {
+    check_index_1d(*tgt, "tgt");
+    TORCH_CHECK(tgt->numel() == n_edge,
+                "segment_transpose: tgt must have one entry per edge");
+  }
+  if (n_edge == 0)
+    return {torch::zeros({n_src + 1}, col.options()),
+            torch::empty({0}, col.options())};
+  TORCH_CHECK(n_src > 0, "segment_transpose: edges but no source rows");
+  auto src_off = torch::empty({n_src + 1}, col.options());
+  auto in_edge = torch::empty({n_edge}, col.options());
+  auto keys = torch::empty({n_edge}, col.options());
+  const torch::Tensor values =
+      tgt.has_value() ? *tgt : torch::arange(n_edge, col.options());
+  unsigned bits = 1;  // 0 <= col < n_src: only these key bits differ
+  while (bits < 63 && ((int64_t)1 << bits) < n_src) ++bits;
+  hipStream_t stream = current_stream();
+  // below 2^20 items rocprim takes its merge sort; forcing Onesweep was
+  // measured slower at the flagship sizes (docs/kernels.md)
+  size_t bytes = 0;
+  GLT_HIP_CHECK(rocprim::radix_sort_pairs(
+      nullptr, bytes, col.data_ptr<int64_t>(), keys.data_ptr<int64_t>(),
+      values.data_ptr<int64_t>(), in_edge.data_ptr<int64_t>(),
+      (size_t)n_edge, 0u, bits, stream));
+  auto tmp = scratch_bytes((int64_t)std::max<size_t>(bytes, 1), col.device());
+  GLT_HIP_CHECK(rocprim::radix_sort_pairs(
+      tmp.data_ptr(), bytes, col.data_ptr<int64_t>(),
+      keys.data_ptr<int64_t>(), values.data_ptr<int64_t>(),
+      in_edge.data_ptr<int64_t>(), (size_t)n_edge, 0u, bits, stream));
+  hipLaunchKernelGGL(seg_boundary_kernel,
+                     dim3(grid_for(std::max(n_edge, n_src + 1))),
+                     dim3(kBlock), 0, stream, keys.data_ptr<int64_t>(),
+                     n_edge, n_src, src_off.data_ptr<int64_t>());
+  return {src_off, in_edge};
+}
+
+torch::Tensor hip_segment_mean_bwd_gather(
+    const torch::Tensor& dy, const torch::Tensor& col,
+    const torch::Tensor& offsets, int64_t n_src, bool order_independent,
+    const torch::Tensor& src_off, const torch::Tensor& in_edge,
+    const c10::optional<torch::Tensor>& mask) {
+  return segment_mean_bwd_gather<false>(dy, col, offsets, n_src,
+                                        order_independent, src_off, in_edge,
+                                        mask);
+}
+
+torch::Tensor hip_segment_mean_cat_bwd_gather(
+    const torch::Tensor& dy, const torch::Tensor& col,
+    const torch::Tensor& offsets, int64_t n_src, bool order_independent,
+    const torch::Tensor& src_off, const torch::Tensor& in_edge,
+    const c10::optional<torch::Tensor>& mask) {
+  return segment_mean_bwd_gather<true>(dy, col, offsets, n_src,
+                                       order_independent, src_off, in_edge,
+                                       mask);
 }
 
 // (out, arg): out is [n_tgt, F] ([n_tgt, 2F] with cat) in x's dtype, arg is

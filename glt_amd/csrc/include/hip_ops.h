@@ -129,6 +129,27 @@ torch::Tensor hip_segment_mean_cat_bwd(const torch::Tensor& dy,
                                        int64_t n_src,
                                        bool order_independent = false);
 
+// Atomic-free backward of the two above.  hip_segment_transpose builds the
+// inverted index of col: in_edge[src_off[s] : src_off[s + 1]] lists the
+// edges with col[e] == s in ascending e, as tgt[e] when tgt is given (the
+// form the gather backward takes) and as e otherwise.  The gather backward
+// sums per source row in fp32 and returns dx [n_src, F] in dy's dtype,
+// every row written; mask ([>= n_src, F], dy's dtype) applies
+// threshold_backward(dx, mask, 0) in the same pass.
+std::tuple<torch::Tensor, torch::Tensor> hip_segment_transpose(
+    const torch::Tensor& col, int64_t n_src,
+    const c10::optional<torch::Tensor>& tgt);
+torch::Tensor hip_segment_mean_bwd_gather(
+    const torch::Tensor& dy, const torch::Tensor& col,
+    const torch::Tensor& offsets, int64_t n_src, bool order_independent,
+    const torch::Tensor& src_off, const torch::Tensor& in_edge,
+    const c10::optional<torch::Tensor>& mask);
+torch::Tensor hip_segment_mean_cat_bwd_gather(
+    const torch::Tensor& dy, const torch::Tensor& col,
+    const torch::Tensor& offsets, int64_t n_src, bool order_independent,
+    const torch::Tensor& src_off, const torch::Tensor& in_edge,
+    const c10::optional<torch::Tensor>& mask);
+
 // Weighted segment sum: out[t] = a[t] * sum_e w[e] * b[col[e]] * x[col[e]]
 // with optional fp32 factors (absent = 1).  bwd returns (dx fp32, dw fp32),
 // each None unless requested; x is only read for dw.  coef_bound: 0-dim

@@ -57,14 +57,36 @@ class SAGEConv(nn.Module):
 
     def forward(self, x, edge_index: torch.Tensor,
                 num_target: int = None, sorted_by_target: bool = True,
-                fuse_relu: bool = False) -> torch.Tensor:
+                fuse_relu: bool = False, relu_input: bool = False,
+                relu_grad_by_consumer: bool = False) -> torch.Tensor:
         """x: [n, F] or (x_target, x_source) for bipartite relations.
         fuse_relu folds the activation into the projection GEMM epilogue
-        (MFMA path); the caller must then skip its own activation."""
+        (MFMA path); the caller must then skip its own activation.
+
+        relu_input / relu_grad_by_consumer move the ReLU mask of a layer
+        boundary from the producer's backward into the consumer's
+        (GraphSAGE.forward sets the pair from one predicate).
+        relu_input: x is a ReLU output whose producer left its mask to
+        this conv; the fused mean aggregation applies it to the gradient
+        of x in the pass that computes it.  relu_grad_by_consumer: this
+        conv's fused-ReLU projection leaves its mask to the one consumer
+        of its output.  A conv that cannot honour a flag on the path it
+        takes raises instead of dropping the mask."""
+        if relu_input and not self.takes_relu_input(x, sorted_by_target):
+            raise ValueError(
+                "SAGEConv: relu_input needs the fused mean aggregation "
+                "with the gather backward (GPU fp32/bf16 tensor input, "
+                "sorted_by_target, aggr='mean', GLT_SEGMENT_BWD unset)")
         if self.aggr != "mean":
+            if relu_grad_by_consumer:
+                raise ValueError("SAGEConv: relu_grad_by_consumer needs "
+                                 "aggr='mean'")
             return self._forward_aggr(x, edge_index, num_target,
                                       sorted_by_target, fuse_relu)
         if isinstance(x, tuple):
+            if relu_grad_by_consumer:
+                raise ValueError("SAGEConv: relu_grad_by_consumer needs a "
+                                 "tensor input")
             x_tgt, x_src = x
             n = num_target if num_target is not None else x_tgt.size(0)
             tgt, src = edge_index[0], edge_index[1]
@@ -93,18 +115,36 @@ class SAGEConv(nn.Module):
             if self.root_weight:
                 from ..ops import segment_mean_cat
 
-                xin = segment_mean_cat(x, tgt, src, n)
+                xin = segment_mean_cat(x, tgt, src, n, relu_input)
             else:
                 from ..ops import segment_mean
 
-                xin = segment_mean(x, tgt, src, n)
+                xin = segment_mean(x, tgt, src, n, relu_input)
         else:
             agg = x.new_zeros(n, x.size(1))
             agg.index_add_(0, tgt, x.index_select(0, src))
             agg = agg / _degree(tgt, n).unsqueeze(1).to(x.dtype)
             xin = torch.cat([agg, x[:n]], dim=1) if self.root_weight \
                 else agg
-        return self._project(xin, fuse_relu)
+        return self._project(xin, fuse_relu, relu_grad_by_consumer)
+
+    def takes_relu_input(self, x, sorted_by_target: bool = True) -> bool:
+        """Whether forward(x, ...) aggregates through the fused mean
+        kernels with the gather backward, the one path that applies a
+        ``relu_input`` mask."""
+        from ..ops.segment import gather_bwd_enabled
+
+        return (self.aggr == "mean" and isinstance(x, torch.Tensor)
+                and x.is_cuda and bool(sorted_by_target)
+                and x.dtype in (torch.float32, torch.bfloat16)
+                and gather_bwd_enabled())
+
+    def projects_with_cast_relu(self, x) -> bool:
+        """Whether forward(x, ..., fuse_relu=True) projects through
+        cast_linear, the one projection that can leave its ReLU mask to
+        the consumer."""
+        return (self.aggr == "mean" and isinstance(x, torch.Tensor)
+                and x.dtype != self.lin.weight.dtype)
 
     def _forward_aggr(self, x, edge_index, num_target, sorted_by_target,
                       fuse_relu):
@@ -135,14 +175,19 @@ class SAGEConv(nn.Module):
             else agg
         return self._project(xin, fuse_relu)
 
-    def _project(self, xin, fuse_relu: bool):
+    def _project(self, xin, fuse_relu: bool,
+                 relu_grad_by_consumer: bool = False):
         from ..ops import cast_linear, mfma_linear, use_mfma_linear
 
         if xin.dtype != self.lin.weight.dtype:
             # reduced-precision compute over fp32 master params (bf16
             # batches from a bf16 feature store)
             return cast_linear(xin, self.lin.weight, self.lin.bias,
-                               relu=fuse_relu)
+                               relu=fuse_relu,
+                               relu_grad_by_consumer=relu_grad_by_consumer)
+        if relu_grad_by_consumer:
+            raise ValueError("SAGEConv: relu_grad_by_consumer needs the "
+                             "cast_linear projection with fuse_relu")
         if use_mfma_linear(xin, self.lin.weight, relu=fuse_relu):
             return mfma_linear(xin, self.lin.weight, self.lin.bias,
                                relu=fuse_relu)

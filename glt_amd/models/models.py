@@ -49,18 +49,52 @@ class GraphSAGE(nn.Module):
         batch, layer l runs only over the rows/edges still reachable from
         the seeds — ~(fan-out) x less compute on the deep layers."""
         L = len(self.convs)
+        masked = False  # this layer applies the previous boundary's mask
         for i, conv in enumerate(self.convs):
             act = i < L - 1  # fused into the projection GEMM epilogue
+            # one decision per boundary, handed to both of its sides
+            defer = act and self._relu_mask_by_consumer(
+                x, conv, self.convs[i + 1])
             trim = _layer_trim(num_sampled_nodes, num_sampled_edges, L, i)
             if trim is not None:
                 n_in, n_edges, n_out = trim
                 x = conv(x[:n_in], edge_index[:, :n_edges],
-                         num_target=n_out, fuse_relu=act)
+                         num_target=n_out, fuse_relu=act, relu_input=masked,
+                         relu_grad_by_consumer=defer)
             else:
-                x = conv(x, edge_index, fuse_relu=act)
+                x = conv(x, edge_index, fuse_relu=act, relu_input=masked,
+                         relu_grad_by_consumer=defer)
+            masked = defer
             if act:
                 x = F.dropout(x, p=self.dropout, training=self.training)
         return x
+
+    def _relu_mask_by_consumer(self, x, conv, nxt) -> bool:
+        """Whether the ReLU mask of the boundary conv -> nxt moves from
+        conv's projection backward into nxt's aggregation backward, where
+        it costs no pass of its own (x is conv's input).
+
+        All of: nxt takes the fused mean aggregation with the gather
+        backward (same device and dtype as x: cast_linear returns x's);
+        conv projects through cast_linear with the fused ReLU; dropout
+        is inactive, so nxt's input IS the ReLU output and ``input <= 0``
+        is the pre-activation's mask; nxt is the activation's only
+        consumer (forward() hands it to nothing else, and rows nxt trims
+        away get zero gradient, which no mask changes).
+
+        forward() evaluates this once per boundary and passes the one
+        result to both sides, so the mask cannot be applied twice or not
+        at all by a disagreement between them; and a conv that cannot
+        honour its flag on the path it actually takes raises (SAGEConv
+        .forward) rather than drop the mask.  If GLT_SEGMENT_BWD changes
+        between forward and backward, the atomic fallback applies the
+        saved mask itself.
+        """
+        if not isinstance(x, torch.Tensor):
+            return False
+        if self.training and self.dropout > 0:
+            return False
+        return conv.projects_with_cast_relu(x) and nxt.takes_relu_input(x)
 
 
 class GAT(nn.Module):

@@ -62,10 +62,17 @@ class _CastLinear(torch.autograd.Function):
     to the input's dtype (hipBLASLt runs the GEMM at the bf16 MFMA rate,
     ~2x fp32); backward produces fp32 grads for the fp32 leaves so Adam
     keeps full-precision state.
+
+    relu_grad_by_consumer (with relu): backward does not apply the ReLU
+    mask; the one consumer of the output does, fused into its own
+    backward (``segment_mean[_cat](..., relu_input=True)``), and the
+    gradient arrives here already masked.  The output is then not kept.
     """
 
     @staticmethod
-    def forward(ctx, x, weight, bias, relu):
+    def forward(ctx, x, weight, bias, relu, relu_grad_by_consumer=False):
+        if relu_grad_by_consumer and not relu:
+            raise ValueError("cast_linear: relu_grad_by_consumer needs relu")
         w16 = weight.to(x.dtype)
         if _use_bf16_mfma(x, weight):
             from .. import _C
@@ -76,22 +83,23 @@ class _CastLinear(torch.autograd.Function):
             out = torch.nn.functional.linear(x, w16, b16)
             if relu:
                 out = torch.relu_(out)
-        if relu:  # out is only needed for the ReLU mask in backward
+        # out is only needed for the ReLU mask in backward
+        ctx.mask_here = relu and not relu_grad_by_consumer
+        if ctx.mask_here:
             ctx.save_for_backward(x, w16, out)
         else:
             ctx.save_for_backward(x, w16)
         ctx.has_bias = bias is not None
-        ctx.relu = relu
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.relu:
+        if ctx.mask_here:
             x, w16, out = ctx.saved_tensors
         else:
             x, w16 = ctx.saved_tensors
         dy = dy.contiguous()
-        if ctx.relu:
+        if ctx.mask_here:
             # one-kernel relu mask (vs gt + mul two-kernel form)
             dy = torch.ops.aten.threshold_backward(dy, out, 0)
         dx = dw = db = None
@@ -118,7 +126,7 @@ class _CastLinear(torch.autograd.Function):
                 db = dy.sum(0).to(torch.float32)
         if ctx.has_bias and ctx.needs_input_grad[2] and db is None:
             db = dy.sum(0).to(torch.float32)
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
 def _use_bf16_mfma(x: torch.Tensor, weight: torch.Tensor) -> bool:
@@ -135,11 +143,14 @@ def _use_bf16_mfma(x: torch.Tensor, weight: torch.Tensor) -> bool:
 
 
 def cast_linear(x: torch.Tensor, weight: torch.Tensor,
-                bias: torch.Tensor = None, relu: bool = False
-                ) -> torch.Tensor:
+                bias: torch.Tensor = None, relu: bool = False,
+                relu_grad_by_consumer: bool = False) -> torch.Tensor:
     """F.linear with the compute in x's (reduced) dtype and fp32 master
-    weights; optional fused-at-the-boundary ReLU."""
-    return _CastLinear.apply(x, weight, bias, relu)
+    weights; optional fused-at-the-boundary ReLU.  relu_grad_by_consumer:
+    the ReLU mask of the backward is applied by the output's one consumer
+    (see _CastLinear); only for a caller that guarantees that consumer."""
+    return _CastLinear.apply(x, weight, bias, relu,
+                             bool(relu_grad_by_consumer))
 
 
 def use_mfma_linear(x: torch.Tensor, weight: torch.Tensor,

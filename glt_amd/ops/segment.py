@@ -8,6 +8,8 @@ primitive; picks the kernels or a torch composition itself.
 segment_max / segment_min (+ _cat) and segment_sum: SAGEConv's other
 aggregators; they pick the kernels or a torch composition the same way.
 """
+import os
+
 import torch
 
 _boundary_cache = {}
@@ -57,23 +59,60 @@ def _from_arena(dx, dy):
     return dx
 
 
+def gather_bwd_enabled() -> bool:
+    """Whether segment_mean[_cat] take the atomic-free gather backward.
+    ``GLT_SEGMENT_BWD=atomic`` (read at every call) keeps the fp32-arena
+    atomic backward, for A/B runs and as a fallback."""
+    return os.environ.get("GLT_SEGMENT_BWD", "") != "atomic"
+
+
+def _segment_mean_bwd(ctx, dy, cat):
+    """dx of segment_mean / segment_mean_cat.
+
+    Default: the inverted index of col is built here, in backward (a
+    layer whose input needs no gradient never pays for it), and one
+    gather kernel sums per source row, rounds to dy's dtype and, with
+    ``relu_input``, masks by the saved input: no arena, no atomics, no
+    separate cast or mask pass.  In deterministic mode the result has
+    the bits of the atomic path below; in plain mode it is run-to-run
+    identical as well (each source's list keeps the edge order), which
+    the atomic path is not.
+    """
+    from .. import _C
+
+    col, offsets, tgt = ctx.saved_tensors[:3]
+    mask = ctx.saved_tensors[3] if ctx.relu_input else None
+    dy = dy.contiguous()
+    if gather_bwd_enabled():
+        src_off, in_tgt = _C.segment_transpose(col, ctx.n_src, tgt)
+        fn = _C.segment_mean_cat_bwd_gather if cat \
+            else _C.segment_mean_bwd_gather
+        return fn(dy, col, offsets, ctx.n_src, is_deterministic(), src_off,
+                  in_tgt, mask)
+    fn = _C.segment_mean_cat_bwd if cat else _C.segment_mean_bwd
+    dx = _from_arena(fn(dy, col, offsets, ctx.n_src, is_deterministic()), dy)
+    if mask is not None:
+        dx = torch.ops.aten.threshold_backward(dx, mask[:ctx.n_src], 0)
+    return dx
+
+
 class _SegmentMean(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, col, offsets, n_src):
+    def forward(ctx, x, col, offsets, n_src, tgt, relu_input):
         from .. import _C
 
-        ctx.save_for_backward(col, offsets)
+        if relu_input:  # x itself is the mask: a reference, no copy
+            ctx.save_for_backward(col, offsets, tgt, x)
+        else:
+            ctx.save_for_backward(col, offsets, tgt)
         ctx.n_src = n_src
+        ctx.relu_input = relu_input
         return _C.segment_mean_fwd(x, col, offsets, offsets.numel() - 1)
 
     @staticmethod
     def backward(ctx, dy):
-        from .. import _C
-
-        col, offsets = ctx.saved_tensors
-        dx = _C.segment_mean_bwd(dy.contiguous(), col, offsets, ctx.n_src,
-                                 is_deterministic())
-        return _from_arena(dx, dy), None, None, None
+        return _segment_mean_bwd(ctx, dy, False), None, None, None, None, \
+            None
 
 
 class _SegmentMeanCat(torch.autograd.Function):
@@ -83,42 +122,49 @@ class _SegmentMeanCat(torch.autograd.Function):
     targets must be the row prefix of x."""
 
     @staticmethod
-    def forward(ctx, x, col, offsets, n_tgt):
+    def forward(ctx, x, col, offsets, n_tgt, tgt, relu_input):
         from .. import _C
 
-        ctx.save_for_backward(col, offsets)
+        if relu_input:
+            ctx.save_for_backward(col, offsets, tgt, x)
+        else:
+            ctx.save_for_backward(col, offsets, tgt)
         ctx.n_src = x.size(0)
+        ctx.relu_input = relu_input
         return _C.segment_mean_cat_fwd(x, col, offsets, n_tgt)
 
     @staticmethod
     def backward(ctx, dy):
-        from .. import _C
-
-        col, offsets = ctx.saved_tensors
-        dx = _C.segment_mean_cat_bwd(dy.contiguous(), col, offsets,
-                                     ctx.n_src, is_deterministic())
-        return _from_arena(dx, dy), None, None, None
+        return _segment_mean_bwd(ctx, dy, True), None, None, None, None, \
+            None
 
 
 def segment_mean(x: torch.Tensor, tgt: torch.Tensor, src: torch.Tensor,
-                 n_tgt: int) -> torch.Tensor:
+                 n_tgt: int, relu_input: bool = False) -> torch.Tensor:
     """Mean of x[src[e]] over contiguous tgt segments.
 
     Requires tgt ascending (glt_amd batches satisfy this); returns
     [n_tgt, F].
+
+    relu_input: x is the output of a ReLU whose own backward was told to
+    leave the mask to its consumer (``cast_linear(...,
+    relu_grad_by_consumer=True)``); the gradient returned for x is then
+    already masked, ``threshold_backward(dx, x, 0)`` (``x <= 0`` is the
+    mask of the pre-activation), in the same pass that computes it.
     """
     offsets = _offsets(tgt, n_tgt)
     return _SegmentMean.apply(x.contiguous(), src.contiguous(), offsets,
-                              x.size(0))
+                              x.size(0), tgt.contiguous(), bool(relu_input))
 
 
 def segment_mean_cat(x: torch.Tensor, tgt: torch.Tensor, src: torch.Tensor,
-                     n_tgt: int) -> torch.Tensor:
+                     n_tgt: int, relu_input: bool = False) -> torch.Tensor:
     """[segment_mean | root] fused: returns [n_tgt, 2F] where the left F
-    columns are the neighbor mean and the right F columns are x[:n_tgt]."""
+    columns are the neighbor mean and the right F columns are x[:n_tgt].
+    relu_input: as in :func:`segment_mean`."""
     offsets = _offsets(tgt, n_tgt)
     return _SegmentMeanCat.apply(x.contiguous(), src.contiguous(), offsets,
-                                 n_tgt)
+                                 n_tgt, tgt.contiguous(), bool(relu_input))
 
 
 class _SegmentExt(torch.autograd.Function):

@@ -97,6 +97,88 @@ def build_flagship_shapes(op, device, bf16=False):
     raise SystemExit(f"unknown op {op}")
 
 
+def seg_bwd_inputs(layer, dtype, device):
+    """Segment-mean backward at the flagship's layer-1 shape (164k source
+    rows, 16.3k targets, 163k edges of hops 1-2) or layer-2 shape (16.3k
+    sources, 1024 targets, 15k edges), F = 256: every source past the
+    targets has one in-edge and the remaining edges land anywhere, which
+    gives the batch's mean in-degree of about 1.1."""
+    torch.manual_seed(0)
+    n_src, n_tgt, E = ((164_000, 16_300, 163_000) if layer == 1
+                       else (16_300, 1024, 15_000))
+    F = 256
+    E = max(E, n_src - n_tgt)
+    tgt = torch.sort(torch.randint(0, n_tgt, (E,), device=device))[0]
+    col = torch.cat([torch.arange(n_tgt, n_src, device=device),
+                     torch.randint(0, n_src, (E - (n_src - n_tgt),),
+                                   device=device)])
+    col = col[torch.randperm(E, device=device)]
+    from glt_amd.ops.segment import _boundaries
+    off = torch.searchsorted(tgt, _boundaries(n_tgt, device))
+    dy = torch.randn(n_tgt, 2 * F, device=device).to(dtype)
+    mask = torch.randn(n_src, F, device=device).relu_().to(dtype)
+    return dy, tgt, col, off, n_src, mask
+
+
+def seg_bwd_table(device, iters, warmup):
+    """--op seg_bwd: the atomic chain (zero fill + atomics, cast to dy's
+    dtype, threshold_backward) against the gather chain (index build +
+    one kernel) of segment_mean_cat's backward, deterministic mode, and
+    the two halves of the gather chain on their own.  us per call from
+    device events over --iters calls."""
+    from glt_amd import _C
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        a = torch.cuda.Event(enable_timing=True)
+        b = torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e3 / iters
+
+    for layer in (1, 2):
+        for dtype in (torch.bfloat16, torch.float32):
+            dy, tgt, col, off, n_src, mask = seg_bwd_inputs(layer, dtype,
+                                                            device)
+            F, sz = mask.size(1), mask.element_size()
+
+            def atomic():
+                dx = _C.segment_mean_cat_bwd(dy, col, off, n_src, True)
+                if dx.dtype != dtype:
+                    dx = dx.to(dtype)
+                return torch.ops.aten.threshold_backward(dx, mask, 0)
+
+            def index():
+                return _C.segment_transpose(col, n_src, tgt)
+
+            src_off, in_tgt = index()
+
+            def kernel():
+                return _C.segment_mean_cat_bwd_gather(
+                    dy, col, off, n_src, True, src_off, in_tgt, mask)
+
+            def gather():
+                so, it = index()
+                return _C.segment_mean_cat_bwd_gather(
+                    dy, col, off, n_src, True, so, it, mask)
+
+            assert torch.equal(atomic(), gather())
+            # the kernel reads dy, the mask and the index, writes dx once
+            nbytes = (dy.numel() + 2 * n_src * F) * sz + \
+                8 * (col.numel() + n_src + 1 + off.numel())
+            t_k = timed(kernel)
+            name = "L%d %s" % (layer, "bf16" if sz == 2 else "fp32")
+            print(f"seg_bwd {name}: atomic chain {timed(atomic):.1f} us, "
+                  f"gather chain {timed(gather):.1f} us (index "
+                  f"{timed(index):.1f} us, kernel {t_k:.1f} us = "
+                  f"{nbytes / 1e6:.1f} MB at {nbytes / t_k / 1e6:.2f} TB/s)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", required=True,
@@ -107,7 +189,8 @@ def main():
                              "gemm_kt_bf16", "seg_mean_cat_bf16",
                              "seg_wsum", "seg_wsum_bf16", "gcn_conv",
                              "gcn_conv_composite", "seg_max", "seg_max_cat",
-                             "sage_conv_max", "sage_conv_max_composite"])
+                             "sage_conv_max", "sage_conv_max_composite",
+                             "seg_bwd"])
     ap.add_argument("--bf16", action="store_true",
                     help="gcn_conv, seg_mean, seg_max and sage_conv_max "
                          "ops: bf16 input at F=100 (default fp32 at F=256)")
@@ -122,6 +205,9 @@ def main():
     import glt_amd
     from glt_amd import _C
 
+    if args.op == "seg_bwd":
+        seg_bwd_table(device, args.iters, args.warmup)
+        return
     inp = build_flagship_shapes(args.op, device, args.bf16)
 
     op = args.op
