@@ -308,6 +308,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gat_fused_bwd", &hip_gat_fused_bwd);
   m.def("gat_multi_fwd", &hip_gat_multi_fwd);
   m.def("gat_multi_bwd", &hip_gat_multi_bwd);
+  m.def("gatv2_fwd", &hip_gatv2_fwd, py::arg("h_tgt"), py::arg("h_src"),
+        py::arg("att"), py::arg("src"), py::arg("offsets"), py::arg("n_tgt"),
+        py::arg("slope"), py::arg("for_backward") = false);
+  m.def("gatv2_bwd", &hip_gatv2_bwd, py::arg("h_tgt"), py::arg("h_src"),
+        py::arg("att"), py::arg("tgt"), py::arg("src"), py::arg("offsets"),
+        py::arg("out"), py::arg("m"), py::arg("z"), py::arg("dout"),
+        py::arg("slope"), py::arg("src_off") = py::none(),
+        py::arg("in_edge") = py::none());
   m.def("segment_mean_fwd", &hip_segment_mean_fwd);
   m.def("segment_mean_bwd", &hip_segment_mean_bwd, py::arg("dy"),
         py::arg("col"), py::arg("offsets"), py::arg("n_src"),

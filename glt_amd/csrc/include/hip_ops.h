@@ -227,6 +227,32 @@ void hip_gat_multi_bwd(const std::vector<torch::Tensor>& h_tgt,
                        double slope,
                        const std::vector<torch::Tensor>& dbias);
 
+// --- fused GATv2 attention (hip_gatv2.hip) ----------------------------------
+// score_e[h] = sum_c att[h,c] * leaky_relu(h_src[src_e,h,c] + h_tgt[t,h,c]),
+// softmax per target segment, out[t] = sum_e p_e * h_src[src_e].  h is fp32
+// or bf16, att fp32 [H, C], 1 <= C <= 128; all arguments are validated
+// before any launch.  fwd returns (out, m, Z, out_f32); nothing per edge is
+// saved.  out_f32 is None unless for_backward; it is the fp32 out the
+// backward takes: out itself for fp32 h, the unrounded accumulator for bf16.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor,
+           c10::optional<torch::Tensor>>
+hip_gatv2_fwd(const torch::Tensor& h_tgt, const torch::Tensor& h_src,
+              const torch::Tensor& att, const torch::Tensor& src,
+              const torch::Tensor& offsets, int64_t n_tgt, double slope,
+              bool for_backward);
+// Atomic-free backward: (dh_tgt, dh_src, datt fp32 [H, C]), dh in h's dtype
+// with every row written; out is the forward's out_f32.  dh_src is
+// computed, by source, only when (src_off, in_edge) =
+// hip_segment_transpose(src, n_src, nullopt) is given, and is None otherwise.
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>, torch::Tensor>
+hip_gatv2_bwd(const torch::Tensor& h_tgt, const torch::Tensor& h_src,
+              const torch::Tensor& att, const torch::Tensor& tgt,
+              const torch::Tensor& src, const torch::Tensor& offsets,
+              const torch::Tensor& out, const torch::Tensor& m,
+              const torch::Tensor& z, const torch::Tensor& dout,
+              double slope, const c10::optional<torch::Tensor>& src_off,
+              const c10::optional<torch::Tensor>& in_edge);
+
 // --- f32 MFMA projection GEMM (hip_gemm_f32.hip) ----------------------------
 torch::Tensor hip_sage_gemm(const torch::Tensor& A, const torch::Tensor& B,
                             const c10::optional<torch::Tensor>& bias,

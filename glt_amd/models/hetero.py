@@ -1,6 +1,6 @@
-"""Heterogeneous models: RGNN (rgat / rsage, as in the reference MLPerf
-IGBH example, reference examples/igbh/rgnn.py capability) and a generic
-HeteroConv combinator."""
+"""Heterogeneous models: RGNN (rgat / rgatv2 / rsage, as in the reference
+MLPerf IGBH example, reference examples/igbh/rgnn.py capability) and a
+generic HeteroConv combinator."""
 from typing import Dict, List, Optional
 
 import torch
@@ -8,7 +8,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..typing import EdgeType, NodeType
-from .layers import GATConv, SAGEConv
+from .layers import GATConv, GATv2Conv, SAGEConv
 
 
 class HeteroConv(nn.Module):
@@ -256,10 +256,11 @@ def conv_bipartite(conv, x_tgt, x_src, edge_index):
 
 
 class RGNN(nn.Module):
-    """Relational GNN over hetero batches; model='rgat' or 'rsage'.
+    """Relational GNN over hetero batches; model='rgat', 'rgatv2' or
+    'rsage'.
 
-    Per layer: per-edge-type conv (GAT or SAGE) summed per target node
-    type, plus a per-node-type self projection so every type advances to
+    Per layer: per-edge-type conv (GAT, GATv2 or SAGE) summed per target
+    node type, plus a per-node-type self projection so every type advances to
     the layer's output dim even when it receives no messages; ReLU/dropout
     between layers; linear head on the predicted node type.
     sage_aggr ('mean' | 'max' | 'min' | 'sum') is the neighbor aggregator
@@ -285,6 +286,10 @@ class RGNN(nn.Module):
                 if model == "rgat":
                     convs[et] = GATConv(dims[li], dims[li + 1] // n_heads,
                                         heads=n_heads, concat=True)
+                elif model == "rgatv2":
+                    # one fused launch per relation: no multi-relation v2
+                    convs[et] = GATv2Conv(dims[li], dims[li + 1] // n_heads,
+                                          heads=n_heads)
                 else:
                     convs[et] = SAGEConv(dims[li], dims[li + 1],
                                          root_weight=False,

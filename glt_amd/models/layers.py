@@ -9,7 +9,7 @@ source/neighbor local index; aggregation flows 1 -> 0.
 Dense math lands on hipBLASLt through torch.nn.Linear (or the in-house
 MFMA GEMM for skinny shapes); sparse aggregation uses the fused HIP
 kernels in csrc/hip/ (segment-mean [+root concat], weighted segment sum,
-GAT edge-softmax) on GPU fp32/bf16 batches, with an index_add_ fallback
+GAT / GATv2 edge-softmax) on GPU fp32/bf16 batches, with an index_add_ fallback
 for CPU/other dtypes.
 """
 
@@ -347,4 +347,101 @@ class GATConv(nn.Module):
             else out.mean(dim=1)
         if self.bias is not None:
             out = out + self.bias
+        return out
+
+
+class GATv2Conv(nn.Module):
+    """Multi-head GATv2 ("dynamic" attention, Brody et al. 2022).
+
+    The score of an edge is ``att . leaky_relu(lin_l(x_src) + lin_r(x_tgt))``
+    per head, a softmax over each target's edges weighs the messages
+    ``lin_l(x_src)``.  Parameter names follow PyG's GATv2Conv (``lin_l``
+    source side, ``lin_r`` target side, ``att`` [1, H, C], ``bias``), so
+    state dicts port; ``share_weights`` makes ``lin_r`` the same module as
+    ``lin_l``.
+
+    GPU fp32 / bf16 batches sorted by target with C <= 128 run the fused
+    HIP kernels (ops.gatv2_softmax_aggregate), whose backward has no float
+    atomics; everything else, and training with dropout > 0, runs the
+    torch composition.  Set ``use_fused = False`` to force the latter.
+
+    Deliberately not a GATConv: HeteroConv sends GATConv relations to the
+    v1 multi-relation kernel, GATv2 relations take the per-relation path.
+    """
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1,
+                 concat: bool = True, negative_slope: float = 0.2,
+                 dropout: float = 0.0, bias: bool = True,
+                 share_weights: bool = False):
+        super().__init__()
+        self.heads = heads
+        self.out_channels = out_channels
+        self.concat = concat
+        self.negative_slope = negative_slope
+        self.dropout = dropout
+        self.share_weights = share_weights
+        self.use_fused = True
+        self.lin_l = nn.Linear(in_channels, heads * out_channels, bias=bias)
+        self.lin_r = self.lin_l if share_weights else \
+            nn.Linear(in_channels, heads * out_channels, bias=bias)
+        self.att = nn.Parameter(torch.empty(1, heads, out_channels))
+        self.bias = nn.Parameter(torch.zeros(
+            heads * out_channels if concat else out_channels)) if bias \
+            else None
+        for lin in {self.lin_l, self.lin_r}:
+            nn.init.xavier_uniform_(lin.weight)
+            if lin.bias is not None:
+                nn.init.zeros_(lin.bias)
+        nn.init.xavier_uniform_(self.att)
+
+    def _project(self, lin, v):
+        if v.dtype != lin.weight.dtype:
+            from ..ops import cast_linear
+
+            h = cast_linear(v, lin.weight, lin.bias)
+        else:
+            h = lin(v)
+        return h.view(v.size(0), self.heads, self.out_channels)
+
+    def forward(self, x, edge_index, num_target: int = None,
+                sorted_by_target: bool = True):
+        """x: [n, F] with the targets as its first ``num_target`` rows, or
+        a (x_target, x_source) tuple for bipartite edge sets;
+        edge_index[0] indexes the target side, edge_index[1] the source
+        side.  ``lin_r`` only runs over the target rows.
+        sorted_by_target: set False for edge sets not sorted by
+        edge_index[0]; they take the composition."""
+        if isinstance(x, tuple):
+            x_tgt, x_src = x
+            nt = num_target if num_target is not None else x_tgt.size(0)
+            h_src = self._project(self.lin_l, x_src)
+            h_tgt = self._project(self.lin_r, x_tgt[:nt])
+        else:
+            nt = num_target if num_target is not None else x.size(0)
+            h_src = self._project(self.lin_l, x)
+            h_tgt = h_src[:nt] if self.share_weights \
+                else self._project(self.lin_r, x[:nt])
+        return self.attend(h_tgt, h_src, edge_index, nt,
+                           sorted_by_target=sorted_by_target)
+
+    def attend(self, h_tgt, h_src, edge_index, nt,
+               sorted_by_target: bool = True):
+        """Attention + aggregation over pre-projected features: h_tgt
+        [>= nt, heads, C] from lin_r, h_src [n, heads, C] from lin_l."""
+        from ..ops import gatv2_composition, gatv2_softmax_aggregate
+
+        tgt, src = edge_index[0], edge_index[1]
+        att = self.att.squeeze(0)
+        if self.training and self.dropout > 0:
+            # no fused attention dropout
+            out = gatv2_composition(h_tgt, h_src, att, tgt, src, nt,
+                                    self.negative_slope, self.dropout)
+        else:
+            out = gatv2_softmax_aggregate(
+                h_tgt, h_src, att, tgt, src, nt, self.negative_slope,
+                sorted_by_target=sorted_by_target and self.use_fused)
+        out = out.reshape(nt, self.heads * self.out_channels) \
+            if self.concat else out.mean(dim=1)
+        if self.bias is not None:
+            out = out + self.bias.to(out.dtype)
         return out

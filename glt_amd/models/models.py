@@ -6,7 +6,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .layers import GATConv, GCNConv, SAGEConv
+from .layers import GATConv, GATv2Conv, GCNConv, SAGEConv
 
 
 def _layer_trim(num_sampled_nodes, num_sampled_edges, num_layers, layer):
@@ -100,15 +100,17 @@ class GraphSAGE(nn.Module):
 class GAT(nn.Module):
     def __init__(self, in_channels: int, hidden_channels: int,
                  num_layers: int, out_channels: Optional[int] = None,
-                 heads: int = 4, dropout: float = 0.0):
+                 heads: int = 4, dropout: float = 0.0, v2: bool = False):
+        """v2: build GATv2Conv ("dynamic" attention) layers."""
         super().__init__()
         out_channels = out_channels or hidden_channels
+        conv = GATv2Conv if v2 else GATConv
         self.convs = nn.ModuleList()
         dim = in_channels
         for i in range(num_layers - 1):
-            self.convs.append(GATConv(dim, hidden_channels, heads=heads))
+            self.convs.append(conv(dim, hidden_channels, heads=heads))
             dim = hidden_channels * heads
-        self.convs.append(GATConv(dim, out_channels, heads=1, concat=False))
+        self.convs.append(conv(dim, out_channels, heads=1, concat=False))
         self.dropout = dropout
 
     def forward(self, x, edge_index, num_sampled_nodes=None,

@@ -3,6 +3,10 @@
 The kernels compute the attention logits internally from (h, att), so the
 python layer never materializes per-node alpha tensors (saves ~8 small
 launches per relation per layer in RGAT's launch-bound regime).
+
+gat_softmax_aggregate / gat_multi_layer: GATv1, fp32-atomic backward.
+gatv2_softmax_aggregate: GATv2, atomic-free backward; picks the kernels or
+the torch composition (gatv2_composition) itself.
 """
 import torch
 
@@ -53,6 +57,117 @@ def gat_softmax_aggregate(h_tgt, h_src, att_src, att_dst, tgt, src, n_tgt,
     offsets = torch.searchsorted(tgt, _boundaries(n_tgt, tgt.device))
     return _GatFused.apply(h_tgt, h_src, att_src, att_dst,
                            src.contiguous(), offsets, negative_slope)
+
+
+class _GatV2Fused(torch.autograd.Function):
+    """GATv2 attention through the hip_gatv2 kernels.
+
+    Forward saves (out in fp32, m, Z) and nothing per edge; backward
+    recomputes the scores.  No gradient is summed with float atomics, so
+    all of them are run-to-run identical whatever ``set_deterministic``
+    says.
+    """
+
+    @staticmethod
+    def forward(ctx, h_tgt, h_src, att, tgt, src, offsets, n_tgt, slope):
+        from .. import _C
+
+        # contiguity once, shared by fwd and the saved tensors bwd reads
+        h_tgt = h_tgt.contiguous()
+        h_src = h_src.contiguous()
+        att = att.contiguous()
+        out, m, z, out_f32 = _C.gatv2_fwd(h_tgt, h_src, att, src, offsets,
+                                          n_tgt, slope,
+                                          any(ctx.needs_input_grad[:3]))
+        ctx.save_for_backward(h_tgt, h_src, att, tgt, src, offsets, out_f32,
+                              m, z)
+        ctx.slope = slope
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from .. import _C
+
+        h_tgt, h_src, att, tgt, src, offsets, out, m, z = ctx.saved_tensors
+        # the by-source index is built here, and only for a source
+        # projection that wants its gradient (layer 1 of a model whose
+        # features need none never pays for it)
+        src_off = in_edge = None
+        if ctx.needs_input_grad[1]:
+            src_off, in_edge = _C.segment_transpose(src, h_src.size(0), None)
+        dht, dhs, datt = _C.gatv2_bwd(h_tgt, h_src, att, tgt, src, offsets,
+                                      out, m, z, dout.contiguous(),
+                                      ctx.slope, src_off, in_edge)
+        return dht, dhs, datt, None, None, None, None, None
+
+
+def gatv2_composition(h_tgt, h_src, att, tgt, src, n_tgt,
+                      negative_slope=0.2, dropout=0.0):
+    """GATv2 attention as a chain of torch ops: any device, any float
+    dtype, any edge order.  It materialises the [E, H, C] pre-activation.
+
+        u_e     = h_src[src_e] + h_tgt[tgt_e]
+        score_e = sum_c att[h, c] * leaky_relu(u_e[h, c])
+        out[t]  = sum_{e: tgt_e = t} softmax_t(score)_e * h_src[src_e]
+
+    Half-precision inputs are computed in fp32 and the result is returned
+    in their dtype.  dropout > 0 drops attention coefficients.
+    """
+    dtype = h_src.dtype
+    if dtype not in (torch.float32, torch.float64):
+        h_tgt, h_src = h_tgt.float(), h_src.float()
+    att = att.to(h_src.dtype)
+    H, C = h_src.size(1), h_src.size(2)
+    # index_select (not advanced indexing): its backward is an index_add
+    hs = h_src.index_select(0, src)
+    u = hs + h_tgt.index_select(0, tgt)
+    score = (torch.nn.functional.leaky_relu(u, negative_slope) * att).sum(-1)
+    s_max = torch.full((n_tgt, H), float("-inf"), device=score.device,
+                       dtype=score.dtype)
+    s_max.scatter_reduce_(0, tgt.unsqueeze(1).expand_as(score),
+                          score.detach(), reduce="amax", include_self=True)
+    # the max is a constant shift of a softmax: no gradient through it
+    ex = (score - s_max.index_select(0, tgt)).exp()
+    denom = ex.new_zeros(n_tgt, H)
+    denom.index_add_(0, tgt, ex)
+    alpha = ex / denom.clamp(min=1e-16).index_select(0, tgt)
+    if dropout > 0:
+        alpha = torch.nn.functional.dropout(alpha, p=dropout)
+    out = hs.new_zeros(n_tgt, H, C)
+    out.index_add_(0, tgt, hs * alpha.unsqueeze(-1))
+    return out.to(dtype)
+
+
+def gatv2_fused_ok(h_tgt, h_src, sorted_by_target=True) -> bool:
+    """Whether gatv2_softmax_aggregate runs the HIP kernels on these."""
+    return (sorted_by_target and h_src.is_cuda and h_tgt.is_cuda
+            and h_src.dtype in (torch.float32, torch.bfloat16)
+            and h_tgt.dtype == h_src.dtype and h_src.dim() == 3
+            and 1 <= h_src.size(2) <= 128)
+
+
+def gatv2_softmax_aggregate(h_tgt, h_src, att, tgt, src, n_tgt,
+                            negative_slope=0.2, sorted_by_target=True):
+    """GATv2 ("dynamic" attention) edge softmax + aggregation.
+
+    out[t,h,:] = sum_e softmax_t(sum_c att[h,c] * leaky(h_src[src_e,h,c] +
+    h_tgt[t,h,c])) * h_src[src_e,h,:].  h_tgt is [>= n_tgt, H, C], h_src
+    [n_src, H, C], att [H, C]; a target without edges gets 0.
+
+    GPU fp32 / bf16 inputs with C <= 128 and edges sorted by target run the
+    fused kernels (forward, and a backward without float atomics: every
+    gradient is bit-reproducible).  Everything else (the CPU, other dtypes,
+    C > 128, sorted_by_target=False) runs gatv2_composition.
+    """
+    if not gatv2_fused_ok(h_tgt, h_src, sorted_by_target):
+        return gatv2_composition(h_tgt, h_src, att, tgt, src, n_tgt,
+                                 negative_slope)
+    from .segment import _offsets
+
+    tgt = tgt.contiguous()
+    return _GatV2Fused.apply(h_tgt, h_src, att.float(), tgt,
+                             src.contiguous(), _offsets(tgt, n_tgt), n_tgt,
+                             negative_slope)
 
 
 class _GatFusedMulti(torch.autograd.Function):

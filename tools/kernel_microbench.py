@@ -179,6 +179,93 @@ def seg_bwd_table(device, iters, warmup):
                   f"{nbytes / 1e6:.1f} MB at {nbytes / t_k / 1e6:.2f} TB/s)")
 
 
+def gatv2_table(device, iters, warmup, rounds=5):
+    """--op gatv2: GATv2 attention forward + backward (all four gradients)
+    at the gat_fused flagship shape, fused kernels against the torch
+    composition, fp32 and bf16.  The two are timed alternately, `rounds`
+    times `iters` calls each, from device events; median and range of the
+    rounds, ms per call.  Then the backward's parts: the by-source index
+    build, the native backward with and without the by-source pass."""
+    from glt_amd import _C
+    from glt_amd.ops import gatv2_composition, gatv2_softmax_aggregate
+    from glt_amd.ops.segment import _offsets
+
+    def timed(fn):
+        a = torch.cuda.Event(enable_timing=True)
+        b = torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / iters
+
+    def spread(ts):
+        ts = sorted(ts)
+        return "%.3f ms (%.3f - %.3f)" % (ts[len(ts) // 2], ts[0], ts[-1])
+
+    h32, att, tgt, src, n_tgt = build_flagship_shapes("gat_fused", device)
+    n_src, H, C = h32.shape
+    cnt = torch.bincount(src, minlength=n_src)
+    print(f"gatv2 shape: n_src {n_src}, n_tgt {n_tgt}, E {src.numel()}, "
+          f"H {H}, C {C}; edges per target: median "
+          f"{int(torch.bincount(tgt, minlength=n_tgt).median())}, max "
+          f"{int(torch.bincount(tgt, minlength=n_tgt).max())}; in-edges per "
+          f"source: median {int(cnt.median())}, median of sources with "
+          f"edges {int(cnt[cnt > 0].median())}, max {int(cnt.max())}, "
+          f"{int((cnt == 0).sum())} sources without edges")
+    hr32 = torch.randn(n_tgt, H, C, device=device)
+    g32 = torch.randn(n_tgt, H, C, device=device)
+    off = _offsets(tgt, n_tgt)
+    for dtype in (torch.float32, torch.bfloat16):
+        name = "bf16" if dtype == torch.bfloat16 else "fp32"
+        hl = h32.to(dtype).requires_grad_(True)
+        hr = hr32.to(dtype).requires_grad_(True)
+        at = att.clone().requires_grad_(True)
+        dout = g32.to(dtype)
+
+        def step(fn):
+            hl.grad = hr.grad = at.grad = None
+            fn(hr, hl, at, tgt, src, n_tgt, 0.2).backward(dout)
+
+        fused = lambda: step(gatv2_softmax_aggregate)
+        comp = lambda: step(gatv2_composition)
+        for _ in range(warmup):
+            fused()
+            comp()
+        tf, tc = [], []
+        for _ in range(rounds):
+            tf.append(timed(fused))
+            tc.append(timed(comp))
+        print(f"gatv2 {name} fwd+bwd: fused {spread(tf)}, composition "
+              f"{spread(tc)}, ratio of medians "
+              f"{sorted(tc)[rounds // 2] / sorted(tf)[rounds // 2]:.2f}x")
+
+        with torch.no_grad():
+            hl_, hr_ = hl.detach(), hr.detach()
+            out, m, z, o32 = _C.gatv2_fwd(hr_, hl_, att, src, off, n_tgt,
+                                          0.2, True)
+            so, ie = _C.segment_transpose(src, n_src, None)
+            fwd = lambda: _C.gatv2_fwd(hr_, hl_, att, src, off, n_tgt, 0.2,
+                                       True)
+            index = lambda: _C.segment_transpose(src, n_src, None)
+            both = lambda: _C.gatv2_bwd(hr_, hl_, att, tgt, src, off, o32,
+                                        m, z, dout, 0.2, so, ie)
+            by_tgt = lambda: _C.gatv2_bwd(hr_, hl_, att, tgt, src, off,
+                                          o32, m, z, dout, 0.2)
+            parts = {"forward": fwd, "index build": index,
+                     "backward, both passes": both,
+                     "backward, by-target pass only (no p/ds stores)":
+                         by_tgt}
+            for fn in parts.values():
+                for _ in range(warmup):
+                    fn()
+            for label, fn in parts.items():
+                print(f"gatv2 {name} {label}: "
+                      f"{spread([timed(fn) for _ in range(rounds)])}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", required=True,
@@ -190,7 +277,7 @@ def main():
                              "seg_wsum", "seg_wsum_bf16", "gcn_conv",
                              "gcn_conv_composite", "seg_max", "seg_max_cat",
                              "sage_conv_max", "sage_conv_max_composite",
-                             "seg_bwd"])
+                             "seg_bwd", "gatv2"])
     ap.add_argument("--bf16", action="store_true",
                     help="gcn_conv, seg_mean, seg_max and sage_conv_max "
                          "ops: bf16 input at F=100 (default fp32 at F=256)")
@@ -207,6 +294,9 @@ def main():
 
     if args.op == "seg_bwd":
         seg_bwd_table(device, args.iters, args.warmup)
+        return
+    if args.op == "gatv2":
+        gatv2_table(device, args.iters, args.warmup)
         return
     inp = build_flagship_shapes(args.op, device, args.bf16)
 
