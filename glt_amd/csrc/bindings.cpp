@@ -292,6 +292,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_bt_bf16", &hip_gemm_bt_bf16, py::arg("A"), py::arg("Bt"),
         py::arg("bias") = py::none(), py::arg("relu") = false,
         py::arg("out_fp32") = false);
+  m.def(
+      "gemm_bt_bf16_plan",
+      [](int64_t M, int64_t K, int64_t N, bool aligned) {
+        const GemmBtPlan p = gemm_bt_bf16_plan(M, K, N, aligned);
+        const char* names[] = {"narrow", "wide", "persist"};
+        return std::make_tuple(std::string(names[p.kernel]), p.grid_x,
+                               p.grid_y);
+      },
+      py::arg("M"), py::arg("K"), py::arg("N"), py::arg("aligned") = true);
+  m.def("gemm_bt_tile_offset", &gemm_bt_tile_offset, py::arg("row"),
+        py::arg("chunk"));
   m.def("gemm_kt_bf16", &hip_gemm_kt_bf16, py::arg("A"), py::arg("B"),
         py::arg("with_db") = false);
   m.def(

@@ -10,6 +10,12 @@
  *       materialization anywhere on the forward path.
  *     - bf16 in, bf16 out, fp32 accumulate, bias+ReLU fused in the
  *       epilogue (kills the separate activation round-trip).
+ *     - two forms with bit-identical results, chosen by
+ *       gemm_bt_bf16_plan: gemm_bt_wide_kernel (64 x 256 tiles: A read
+ *       once, next K step prefetched across the MFMAs, swizzled 16-byte
+ *       LDS traffic, whole-line stores) for the large projections, and
+ *       the 64x64 gemm_bt_kernel for everything it cannot take (K not a
+ *       multiple of 8, N < 128) or M too small to fill the CUs.
  *  2. gemm_kt_kernel:  dW[M,N] = A[Kb,M]^T @ B[Kb,N], db[M] = colsum(A)
  *     - the weight-gradient shape (K huge = batch rows): split-K over
  *       grid.z into per-chunk partial planes (a torch sum folds them);
@@ -36,6 +42,7 @@
  * transposing kernel it replaces.
  */
 #include <cstdlib>
+#include <string>
 
 #include "hip_common.h"
 #include "../include/common.h"
@@ -298,6 +305,234 @@ void gemm_bt_persist_kernel(const __bf16* __restrict__ A,
         }
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Wide forward tile: BM rows x 256 columns per workgroup, BM / 16 waves as
+// (BM / 64) x 4, each wave a 64x64 tile of 4x4 16x16 fragments.  At
+// N <= 256 every A row is fetched by exactly one workgroup; for N > 256
+// the column block is the fast index of the 1-D grid, so the workgroups
+// that share an A row tile are neighbours and the second read hits in L2.
+//
+// A and Bt are K-innermost in memory, so a 64-wide K step of either is
+// staged as it is loaded: 16-byte LDS writes of the 16-byte global loads
+// into a [row][64] image with 128-byte rows, XOR-swizzled (bt_tile_off),
+// and 16-byte fragment reads.  The loads of step i+1 are issued into
+// registers right after the barrier of step i and written to LDS after
+// its MFMAs.  The MFMA, the lane-to-k map (lane group g holds
+// k = kk + 8g .. +7) and the ascending kk order are those of
+// gemm_bt_kernel, and a kk step of nothing but zero padding that is
+// skipped here adds +0 there: outputs are bit-for-bit the same.
+// ---------------------------------------------------------------------------
+constexpr int WBN = 256;                   // output columns per workgroup
+constexpr int BT_ROW_BYTES = GBK * 2;      // one staged row: 64 k
+constexpr int BT_EP_LD = 68;               // epilogue row stride in floats
+
+// Byte offset of 16-byte chunk `ch` (0..7: k = 8 ch .. 8 ch + 7) of row
+// `row` in a staged image.  Rows are 128 bytes, so two rows fill the 64
+// banks once; XOR-ing the chunk with bits 1..3 of the row makes the eight
+// rows of one parity in any aligned 16-row block start in eight different
+// 16-byte slots.  The 8 lanes of a 16-byte store group write the 8 chunks
+// of one row (a permutation of the 8 slots), and the 16 lanes of a
+// 16-byte read group, 8 rows at chunk c and 8 at chunk c ^ 1 of one
+// aligned 16-row block, cover all 64 banks exactly once.
+__host__ __device__ constexpr int bt_tile_off(int row, int ch) {
+  return BT_ROW_BYTES * row + 16 * (ch ^ ((row >> 1) & 7));
+}
+
+// This thread's 16-byte chunks of the K step at k0: chunk s_ch of rows
+// row0 + s_row + RPP * h of X[rows, K].  bt_issue only starts the loads,
+// without a branch: a row past `rows` reads the last row and a chunk past
+// K reads chunk 0 (both in bounds: rows >= 1, K >= 32 and K % 8 == 0 on
+// this path, so a chunk is wholly inside K or wholly outside).  bt_finish,
+// at LDS-write time, zeroes what was out of range: the image is
+// zero-padded, never masked.
+template <int NV, int RPP>
+__device__ __forceinline__ void bt_issue(const __bf16* __restrict__ X,
+                                         int64_t rows, int64_t K,
+                                         int64_t row0, int64_t k0, int s_row,
+                                         int s_ch, bf16x8 (&v)[NV]) {
+  const int64_t k = k0 + s_ch * 8;
+  const int64_t kc = k + 8 <= K ? k : 0;
+#pragma unroll
+  for (int h = 0; h < NV; ++h) {
+    const int64_t g_row = std::min<int64_t>(row0 + s_row + RPP * h, rows - 1);
+    v[h] = *reinterpret_cast<const bf16x8*>(&X[g_row * K + kc]);
+  }
+}
+
+template <int NV, int RPP>
+__device__ __forceinline__ void bt_finish(int64_t rows, int64_t K,
+                                          int64_t row0, int64_t k0, int s_row,
+                                          int s_ch, bf16x8 (&v)[NV]) {
+  const bool k_in = k0 + s_ch * 8 + 8 <= K;
+#pragma unroll
+  for (int h = 0; h < NV; ++h)
+    if (!(k_in && row0 + s_row + RPP * h < rows)) v[h] = bf16x8{};
+}
+
+template <int BM, bool RELU, bool BF16_OUT>
+__global__ __launch_bounds__(BM * 4)
+void gemm_bt_wide_kernel(const __bf16* __restrict__ A,
+                         const __bf16* __restrict__ Bt,
+                         const float* __restrict__ bias,
+                         void* __restrict__ Cv,
+                         int64_t M, int64_t K, int64_t N, int n_blk) {
+  constexpr int NT = BM * 4;               // threads
+  constexpr int RPP = NT / 8;              // rows one staging pass covers
+  constexpr int NA = BM / RPP, NB = WBN / RPP;
+  static_assert(BM % 64 == 0 && NA >= 1, "whole 64-row wave tiles");
+  // A image, then the Bt image; the epilogue reuses the front of it
+  alignas(16) __shared__ unsigned char smem[(BM + WBN) * BT_ROW_BYTES];
+  static_assert((NT / 64) * 16 * BT_EP_LD * 4 <= (BM + WBN) * BT_ROW_BYTES,
+                "epilogue tiles fit in the staging buffers");
+  unsigned char* const As = smem;
+  unsigned char* const Bs = smem + BM * BT_ROW_BYTES;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wm = wave >> 2;                // 64-row wave tile
+  const int wn = wave & 3;                 // 64-col wave tile
+
+  const int64_t block_col = (int64_t)(blockIdx.x % n_blk) * WBN;
+  const int64_t block_row = (int64_t)(blockIdx.x / n_blk) * BM;
+  // a wave whose 64 columns all lie past N multiplies nothing
+  const bool live = block_col + wn * 64 < N;
+
+  f32x4b acc[4][4] = {};
+
+  // staging: 8 lanes take the 8 chunks of one row
+  const int s_row = tid >> 3;
+  const int s_ch = tid & 7;
+  const int fi = lane & 15;                // fragment row / col
+  const int fg = lane >> 4;                // fragment k group
+
+  bf16x8 va[NA], vb[NB];
+  if (K > 0) {
+    bt_issue<NA, RPP>(A, M, K, block_row, 0, s_row, s_ch, va);
+    bt_issue<NB, RPP>(Bt, N, K, block_col, 0, s_row, s_ch, vb);
+  }
+
+  for (int64_t k0 = 0; k0 < K; k0 += GBK) {
+    bt_finish<NA, RPP>(M, K, block_row, k0, s_row, s_ch, va);
+    bt_finish<NB, RPP>(N, K, block_col, k0, s_row, s_ch, vb);
+#pragma unroll
+    for (int h = 0; h < NA; ++h)
+      *reinterpret_cast<bf16x8*>(
+          As + bt_tile_off(s_row + RPP * h, s_ch)) = va[h];
+#pragma unroll
+    for (int h = 0; h < NB; ++h)
+      *reinterpret_cast<bf16x8*>(
+          Bs + bt_tile_off(s_row + RPP * h, s_ch)) = vb[h];
+    __syncthreads();
+    if (k0 + GBK < K) {
+      bt_issue<NA, RPP>(A, M, K, block_row, k0 + GBK, s_row, s_ch, va);
+      bt_issue<NB, RPP>(Bt, N, K, block_col, k0 + GBK, s_row, s_ch, vb);
+    }
+
+#pragma unroll
+    for (int kk = 0; kk < GBK; kk += 32) {
+      // a kk step past K holds only zero padding
+      if (live && k0 + kk < K) {
+        bf16x8 a[4], b[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          a[i] = *reinterpret_cast<const bf16x8*>(
+              As + bt_tile_off(wm * 64 + i * 16 + fi, (kk >> 3) + fg));
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          b[j] = *reinterpret_cast<const bf16x8*>(
+              Bs + bt_tile_off(wn * 64 + j * 16 + fi, (kk >> 3) + fg));
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                a[i], b[j], acc[i][j], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+
+  // Epilogue.  C/D: col = lane & 15, row = (lane >> 4) * 4 + reg.  Bias
+  // and ReLU in fp32 as in gemm_bt_kernel, then each wave passes its
+  // 64x64 tile, 16 rows at a time, through its own [16][68] fp32 LDS tile
+  // (the staging buffers: every wave is past the last barrier above) and
+  // writes whole row pieces, 16 bytes per lane: 8 lanes a 128-byte row
+  // piece of bf16 (rounded once, here), 16 lanes 256 bytes of fp32.  The
+  // 68-float stride puts the two rows a 32-lane half writes 16 banks
+  // apart.  A row of C starts 16-byte aligned only if N is a multiple of
+  // 8 (bf16) or 4 (fp32); otherwise, and in the N tail, elements are
+  // stored one by one.
+  float* const ep = reinterpret_cast<float*>(smem) + wave * (16 * BT_EP_LD);
+  float bv[4] = {0.f, 0.f, 0.f, 0.f};
+  if (bias != nullptr) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t col = block_col + wn * 64 + j * 16 + fi;
+      if (col < N) bv[j] = bias[col];
+    }
+  }
+  constexpr int CPL = BF16_OUT ? 8 : 4;    // columns per lane
+  constexpr int LPR = 64 / CPL;            // lanes per 64-column row piece
+  constexpr int RPI = 64 / LPR;            // rows per wave instruction
+  const bool vec_ok = N % CPL == 0;
+  const int e_row = lane / LPR;
+  const int e_col = (lane % LPR) * CPL;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = acc[i][j][r];
+        if (bias != nullptr) v += bv[j];
+        if (RELU) v = v > 0.f ? v : 0.f;
+        ep[(fg * 4 + r) * BT_EP_LD + j * 16 + fi] = v;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int h = 0; h < 16 / RPI; ++h) {
+      const int rr = e_row + RPI * h;
+      const int64_t row = block_row + wm * 64 + i * 16 + rr;
+      const int64_t col = block_col + wn * 64 + e_col;
+      const float* src = ep + rr * BT_EP_LD + e_col;
+      const f32x4b lo = *reinterpret_cast<const f32x4b*>(src);
+      if (BF16_OUT) {
+        const f32x4b hi = *reinterpret_cast<const f32x4b*>(src + 4);
+        bf16x8 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          o[e] = f2bf(lo[e]);
+          o[4 + e] = f2bf(hi[e]);
+        }
+        __bf16* dst = reinterpret_cast<__bf16*>(Cv) + row * N + col;
+        if (row < M) {
+          if (vec_ok && col + 7 < N) {
+            *reinterpret_cast<bf16x8*>(dst) = o;
+          } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              if (col + e < N) dst[e] = o[e];
+          }
+        }
+      } else {
+        float* dst = reinterpret_cast<float*>(Cv) + row * N + col;
+        if (row < M) {
+          if (vec_ok && col + 3 < N) {
+            *reinterpret_cast<f32x4b*>(dst) = lo;
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              if (col + e < N) dst[e] = lo[e];
+          }
+        }
+      }
+    }
+    __syncthreads();
   }
 }
 
@@ -684,6 +919,61 @@ __global__ void selftest_16x16x32(const __bf16* A, const __bf16* B,
 
 }  // namespace
 
+// Rows per workgroup of the wide kernel: 64 (4 waves, 40 KB of LDS, 3
+// workgroups per CU) measured faster than 128 (8 waves, 48 KB) at every
+// shape and M tried.  BT_WIDE_MIN_M is the M from which the plan takes the
+// wide kernel: 192 row tiles, three quarters of the 256 CUs.  Measured at
+// the three call shapes of the training step: from 16.3k rows up the wide
+// kernel wins at all three, at 12288 it wins one, ties one and loses one
+// by 4%, and at 8192 and below the 64x64 kernel, with four times the
+// workgroups, wins two of three (profiles/r06_gemm_bt_wide_kernels.md).
+constexpr int WBM = 64;
+constexpr int64_t BT_WIDE_MIN_M = 12288;
+
+// Which kernel hip_gemm_bt_bf16 launches for a shape, and its grid (host
+// arithmetic and two environment reads; the launcher calls it and the
+// tests read it).  `aligned`: all three base pointers are 16-byte aligned.
+GemmBtPlan gemm_bt_bf16_plan(int64_t M, int64_t K, int64_t N, bool aligned) {
+  GemmBtPlan p;
+  p.kernel = GemmBtPlan::NARROW;
+  p.grid_x = (M + GBM - 1) / GBM;
+  p.grid_y = (N + GBN - 1) / GBN;
+  if (M <= 0 || N <= 0) return p;  // the launcher returns before it plans
+  if (K <= PKP && std::getenv("GLT_GEMM_PERSIST") != nullptr) {
+    p.kernel = GemmBtPlan::PERSIST;
+    p.grid_x = std::min<int64_t>(p.grid_x, 1024);
+    return p;
+  }
+  bool want = M >= BT_WIDE_MIN_M;
+  if (const char* e = std::getenv("GLT_GEMM_BT")) {
+    const std::string v(e);
+    TORCH_CHECK(v == "wide" || v == "narrow",
+                "GLT_GEMM_BT must be wide or narrow, got '", v, "'");
+    want = v == "wide";
+  }
+  const bool can = K % 8 == 0 && K >= 32 && N >= 128 && aligned;
+  if (want && can) {
+    const int64_t wg = (M + WBM - 1) / WBM * ((N + WBN - 1) / WBN);
+    // 1-D grid, column block fastest; beyond 2^31 - 1 workgroups (M in
+    // the tens of billions) the 64x64 kernel's 2-D grid is the one left
+    if (wg <= 0x7fffffff) {
+      p.kernel = GemmBtPlan::WIDE;
+      p.grid_x = wg;
+      p.grid_y = 1;
+    }
+  }
+  return p;
+}
+
+// Byte offset of 16-byte chunk `chunk` of row `row` in the wide kernel's
+// staged [rows][64] bf16 LDS images (A: 64 rows, Bt: 256 rows; one
+// function for both, the one the kernel stores and reads through).
+int64_t gemm_bt_tile_offset(int64_t row, int64_t chunk) {
+  TORCH_CHECK(row >= 0 && row < WBN && chunk >= 0 && chunk < GBK / 8,
+              "row in [0, 256) and chunk in [0, 8) required");
+  return bt_tile_off((int)row, (int)chunk);
+}
+
 // C = act(A @ Bt^T + bias): A [M,K] bf16, Bt [N,K] bf16 (nn.Linear
 // weight layout), bias fp32 or none.
 torch::Tensor hip_gemm_bt_bf16(const torch::Tensor& A,
@@ -709,16 +999,39 @@ torch::Tensor hip_gemm_bt_bf16(const torch::Tensor& A,
     bias_f = bias->to(torch::kFloat32).contiguous();
     bias_p = bias_f.data_ptr<float>();
   }
-  // NOTE: a persistent-B variant (whole <=256-K weight tile staged once,
-  // A streaming with one sync pair per m-tile) measured SLOWER: its
-  // 68 KB LDS footprint halves occupancy (2 WGs/CU vs 4+) and the lost
-  // latency hiding on the A stream outweighs the saved syncs/B-restage
-  // (L0 fwd 167 us vs 112; flagship 661 vs 720 b/s).  Enable with
-  // GLT_GEMM_PERSIST=1 for further experiments.
-  if (K <= PKP && std::getenv("GLT_GEMM_PERSIST") != nullptr) {
-    const int64_t m_t = (M + GBM - 1) / GBM;
-    dim3 grid((uint32_t)std::min<int64_t>(m_t, 1024),
-              (uint32_t)((N + GBN - 1) / GBN));
+  // Dispatch (gemm_bt_bf16_plan): the wide kernel, BM x 256 tiles that
+  // read A once, prefetch the next K step across the MFMAs and store
+  // whole lines, wherever it applies (K % 8 == 0, K >= 32, N >= 128,
+  // 16-byte aligned operands) and M is large enough to fill the CUs with
+  // such tiles; the 64x64 kernel otherwise.  GLT_GEMM_BT=wide|narrow
+  // overrides the M threshold only.  GLT_GEMM_PERSIST=1 (K <= 256) takes
+  // precedence and selects the persistent-B experiment: whole weight
+  // tile staged once, A streaming with one sync pair per m-tile.  It
+  // measured SLOWER than the 64x64 kernel (L0 fwd 167 us vs 112): its
+  // 68 KB of LDS halve the occupancy, and what it saves, the re-staging
+  // of an L2-resident W, was never the cost; the A re-read, the missing
+  // prefetch and the 2-byte stores were, and it keeps all three.
+  const bool aligned =
+      reinterpret_cast<uintptr_t>(Ac.data_ptr()) % 16 == 0 &&
+      reinterpret_cast<uintptr_t>(Bc.data_ptr()) % 16 == 0 &&
+      reinterpret_cast<uintptr_t>(C.data_ptr()) % 16 == 0;
+  const GemmBtPlan p = gemm_bt_bf16_plan(M, K, N, aligned);
+  if (p.kernel == GemmBtPlan::WIDE) {
+    auto* kfn = out_fp32
+                    ? (relu ? gemm_bt_wide_kernel<WBM, true, false>
+                            : gemm_bt_wide_kernel<WBM, false, false>)
+                    : (relu ? gemm_bt_wide_kernel<WBM, true, true>
+                            : gemm_bt_wide_kernel<WBM, false, true>);
+    hipLaunchKernelGGL(kfn, dim3((uint32_t)p.grid_x), dim3(WBM * 4), 0,
+                       current_stream(),
+                       reinterpret_cast<const __bf16*>(Ac.data_ptr()),
+                       reinterpret_cast<const __bf16*>(Bc.data_ptr()),
+                       bias_p, C.data_ptr(), M, K, N,
+                       (int)((N + WBN - 1) / WBN));
+    return C;
+  }
+  if (p.kernel == GemmBtPlan::PERSIST) {
+    dim3 grid((uint32_t)p.grid_x, (uint32_t)p.grid_y);
     auto* kfn = out_fp32
                     ? (relu ? gemm_bt_persist_kernel<true, false>
                             : gemm_bt_persist_kernel<false, false>)
@@ -730,8 +1043,7 @@ torch::Tensor hip_gemm_bt_bf16(const torch::Tensor& A,
                        bias_p, C.data_ptr(), M, K, N);
     return C;
   }
-  dim3 grid((uint32_t)((M + GBM - 1) / GBM),
-            (uint32_t)((N + GBN - 1) / GBN));
+  dim3 grid((uint32_t)p.grid_x, (uint32_t)p.grid_y);
   auto* kfn = out_fp32
                   ? (relu ? gemm_bt_kernel<true, false>
                           : gemm_bt_kernel<false, false>)

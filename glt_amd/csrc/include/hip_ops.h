@@ -264,6 +264,17 @@ torch::Tensor hip_gemm_bt_bf16(const torch::Tensor& A,
                                const torch::Tensor& Bt,
                                const c10::optional<torch::Tensor>& bias,
                                bool relu, bool out_fp32);
+// The launcher's own dispatch for a shape: the wide BM x 256 kernel, the
+// 64x64 kernel or the persistent-B experiment, and the launch grid.
+struct GemmBtPlan {
+  enum Kernel { NARROW = 0, WIDE = 1, PERSIST = 2 };
+  Kernel kernel;
+  int64_t grid_x, grid_y;
+};
+GemmBtPlan gemm_bt_bf16_plan(int64_t M, int64_t K, int64_t N,
+                             bool aligned = true);
+// Byte offset of a 16-byte chunk in the wide kernel's LDS tile images.
+int64_t gemm_bt_tile_offset(int64_t row, int64_t chunk);
 // (dW, db) = (A[Kb,M]^T @ B[Kb,N], colsum A), fp32 outputs (split-K).
 std::tuple<torch::Tensor, c10::optional<torch::Tensor>> hip_gemm_kt_bf16(
     const torch::Tensor& A, const torch::Tensor& B, bool with_db);
