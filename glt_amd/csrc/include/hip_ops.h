@@ -202,7 +202,8 @@ hip_gat_fused_bwd(const torch::Tensor& h_tgt, const torch::Tensor& h_src,
                   double slope);
 
 // Multi-relation fused GAT: one launch per hetero layer; h views may be
-// row-strided slices of the per-type batched projection.
+// row-strided slices of the per-type batched projection.  The single entry
+// points above are its one-relation case and launch the same kernels.
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 hip_gat_multi_fwd(const std::vector<torch::Tensor>& h_tgt,
                   const std::vector<torch::Tensor>& h_src,
@@ -224,8 +225,7 @@ void hip_gat_multi_bwd(const std::vector<torch::Tensor>& h_tgt,
                        const std::vector<torch::Tensor>& dh_src,
                        const std::vector<torch::Tensor>& datt_src,
                        const std::vector<torch::Tensor>& datt_dst,
-                       double slope,
-                       const std::vector<torch::Tensor>& dbias);
+                       double slope);
 
 // --- fused GATv2 attention (hip_gatv2.hip) ----------------------------------
 // score_e[h] = sum_c att[h,c] * leaky_relu(h_src[src_e,h,c] + h_tgt[t,h,c]),

@@ -78,10 +78,10 @@ class HeteroConv(nn.Module):
     def _multi_gat(self, x_dict, rels, self_lins=None, self_out=None):
         """All relations' attention in ONE fused kernel launch per layer
         (RGAT is launch-bound: ~285 kernels/step measured round 2).  The
-        per-type batched projection is consumed in place via strided
-        views and the backward accumulates one dh arena per type, so the
-        per-relation .contiguous() copies, slice-grad zeros and adds all
-        disappear.  Returns None when preconditions fail (mixed heads /
+        kernels read contiguous per-relation copies of the per-type
+        batched projection's column slices; the backward accumulates one
+        strided dh arena per type, so the per-relation slice-grad zeros
+        and adds disappear.  Returns None when preconditions fail (mixed heads /
         dims, CPU, dropout-in-training, >8 relations) so the caller
         falls back to the per-relation path."""
         if len(rels) > 8:

@@ -170,13 +170,31 @@ def gatv2_softmax_aggregate(h_tgt, h_src, att, tgt, src, n_tgt,
                              negative_slope)
 
 
+def _multi_unpack(spec, n_rel, n_type, tensors):
+    """gat_multi_layer's flat *tensors as (att_src, att_dst, biases,
+    h_types, srcs, offs) and the contiguous fp32 [H, C] att lists the
+    kernels take."""
+    att_src = list(tensors[:n_rel])
+    att_dst = list(tensors[n_rel:2 * n_rel])
+    biases = list(tensors[2 * n_rel:3 * n_rel])  # empty = no bias
+    h_types = list(tensors[3 * n_rel:3 * n_rel + n_type])
+    rest = tensors[3 * n_rel + n_type:]
+    srcs = list(rest[:n_rel])
+    offs = list(rest[n_rel:2 * n_rel])
+    H, C = spec["H"], spec["C"]
+    as_f = [a.reshape(H, C).float().contiguous() for a in att_src]
+    ad_f = [a.reshape(H, C).float().contiguous() for a in att_dst]
+    return att_src, att_dst, biases, h_types, srcs, offs, as_f, ad_f
+
+
 class _GatFusedMulti(torch.autograd.Function):
     """ONE fused attention launch per hetero layer across relations.
 
     Inputs are the per-TYPE batched projection tensors [N_t, R_t*H*C]
-    (consumed in place via strided views — no per-relation .contiguous()
-    copies) plus the per-relation attention parameters; the backward
-    emits ONE dh arena per type (relations accumulate atomically), so
+    plus the per-relation attention parameters.  The kernels READ
+    contiguous per-relation copies of the projection's column slices;
+    only the gradients are strided: the backward emits ONE dh arena per
+    type (relations accumulate atomically into their column slices), so
     the per-relation slice-grad zeros/adds disappear entirely.
     """
 
@@ -184,16 +202,10 @@ class _GatFusedMulti(torch.autograd.Function):
     def forward(ctx, slope, spec, n_rel, n_type, *tensors):
         from .. import _C
 
-        att_src = list(tensors[:n_rel])
-        att_dst = list(tensors[n_rel:2 * n_rel])
-        biases = list(tensors[2 * n_rel:3 * n_rel])  # empty = no bias
-        h_types = list(tensors[3 * n_rel:3 * n_rel + n_type])
-        rest = tensors[3 * n_rel + n_type:]
-        srcs = list(rest[:n_rel])
-        offs = list(rest[n_rel:2 * n_rel])
+        (_, _, biases, h_types, srcs, offs, as_f,
+         ad_f) = _multi_unpack(spec, n_rel, n_type, tensors)
         H, C = spec["H"], spec["C"]
         ht_views, hs_views = [], []
-        as_f, ad_f, b_f = [], [], []
         for r in range(n_rel):
             tt, c0t, st, c0s = spec["rels"][r]
             ht = h_types[tt]
@@ -206,9 +218,7 @@ class _GatFusedMulti(torch.autograd.Function):
                             .contiguous().view(ht.size(0), H, C))
             hs_views.append(hs[:, c0s:c0s + H * C]
                             .contiguous().view(hs.size(0), H, C))
-            as_f.append(att_src[r].reshape(H, C).float().contiguous())
-            ad_f.append(att_dst[r].reshape(H, C).float().contiguous())
-            b_f.append(biases[r].reshape(-1).float().contiguous())
+        b_f = [b.reshape(-1).float().contiguous() for b in biases]
         out, m, z, spre = _C.gat_multi_fwd(ht_views, hs_views, as_f, ad_f,
                                            srcs, offs, slope, b_f)
         ctx.save_for_backward(out, m, z, spre, *tensors)
@@ -222,24 +232,16 @@ class _GatFusedMulti(torch.autograd.Function):
 
         out, m, z, spre, *tensors = ctx.saved_tensors
         slope, spec, n_rel, n_type = ctx.meta
-        att_src = list(tensors[:n_rel])
-        att_dst = list(tensors[n_rel:2 * n_rel])
-        biases = list(tensors[2 * n_rel:3 * n_rel])
-        h_types = list(tensors[3 * n_rel:3 * n_rel + n_type])
-        rest = tensors[3 * n_rel + n_type:]
-        srcs = list(rest[:n_rel])
-        offs = list(rest[n_rel:2 * n_rel])
+        (att_src, att_dst, biases, h_types, srcs, offs, as_f,
+         ad_f) = _multi_unpack(spec, n_rel, n_type, tensors)
         H, C = spec["H"], spec["C"]
         dh_arenas = [torch.zeros(h.size(), dtype=torch.float32,
                                  device=h.device) for h in h_types]
         das = torch.zeros(n_rel, H, C, dtype=torch.float32,
                           device=out.device)
         dad = torch.zeros_like(das)
-        dbias = torch.zeros(n_rel, H * C, dtype=torch.float32,
-                            device=out.device)
         ht_views, hs_views = ctx.h_views
         dht_views, dhs_views = [], []
-        as_f, ad_f, das_v, dad_v = [], [], [], []
         for r in range(n_rel):
             tt, c0t, st, c0s = spec["rels"][r]
             ht, hs = h_types[tt], h_types[st]
@@ -247,31 +249,20 @@ class _GatFusedMulti(torch.autograd.Function):
                 dh_arenas[tt][:, c0t:c0t + H * C].view(ht.size(0), H, C))
             dhs_views.append(
                 dh_arenas[st][:, c0s:c0s + H * C].view(hs.size(0), H, C))
-            as_f.append(att_src[r].reshape(H, C).float().contiguous())
-            ad_f.append(att_dst[r].reshape(H, C).float().contiguous())
-            das_v.append(das[r])
-            dad_v.append(dad[r])
+        _C.gat_multi_bwd(ht_views, hs_views, as_f, ad_f, srcs, offs,
+                         out, m, z, spre, dout, dht_views, dhs_views,
+                         list(das), list(dad), slope)
         # bias grad via one tree-reduction per biased relation (an
         # in-kernel atomic colsum measured catastrophically contended:
         # every (t, h) wave hits the same H*C floats)
-        _C.gat_multi_bwd(ht_views, hs_views, as_f, ad_f, srcs, offs,
-                         out, m, z, spre, dout, dht_views, dhs_views,
-                         das_v, dad_v, slope, [])
-        nt_sizes = [o.numel() - 1 for o in offs]
-        dsplit = torch.split(dout, nt_sizes, dim=0)
-        for r in range(n_rel):
-            if biases[r].numel():
-                dbias[r] = dsplit[r].float().sum(dim=0).reshape(-1)
-        grads = []
-        for r in range(n_rel):
-            grads.append(das[r].reshape(att_src[r].shape)
-                         .to(att_src[r].dtype))
-        for r in range(n_rel):
-            grads.append(dad[r].reshape(att_dst[r].shape)
-                         .to(att_dst[r].dtype))
-        for r in range(n_rel):
-            grads.append(dbias[r].to(biases[r].dtype)
-                         if biases[r].numel() else None)
+        dsplit = torch.split(dout, [o.numel() - 1 for o in offs], dim=0)
+        grads = [das[r].reshape(att_src[r].shape).to(att_src[r].dtype)
+                 for r in range(n_rel)]
+        grads += [dad[r].reshape(att_dst[r].shape).to(att_dst[r].dtype)
+                  for r in range(n_rel)]
+        grads += [dsplit[r].float().sum(dim=0).reshape(biases[r].shape)
+                  .to(biases[r].dtype) if biases[r].numel() else None
+                  for r in range(n_rel)]
         for t in range(n_type):
             grads.append(dh_arenas[t].to(h_types[t].dtype))
         grads.extend([None] * (2 * n_rel))  # srcs, offs

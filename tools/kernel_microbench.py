@@ -42,7 +42,7 @@ def build_flagship_shapes(op, device, bf16=False):
         tgt = torch.sort(torch.randint(0, n_tgt, (E,), device=device))[0]
         src = torch.randint(0, n_src, (E,), device=device)
         return (x, tgt, src, n_tgt)
-    if op == "gat_fused":
+    if op in ("gat_fused", "gat_fused_bwd"):
         H, C = 4, 64
         h = torch.randn(n_src, H, C, device=device)
         att = torch.randn(H, C, device=device)
@@ -270,6 +270,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", required=True,
                     choices=["seg_mean", "seg_mean_cat", "gat_fused",
+                             "gat_fused_bwd",
                              "mfma_gemm", "gather", "sample",
                              "sample_weighted", "sample_weighted_nr",
                              "sample_weighted_hub", "gemm_bt_bf16",
@@ -316,6 +317,18 @@ def main():
         h, att, tgt, src, n_tgt = inp
         off = torch.searchsorted(tgt, _boundaries(n_tgt, device))
         fn = lambda: _C.gat_fused_fwd(h, h, att, att, src, off, 0.2)
+    elif args.op == "gat_fused_bwd":
+        # the backward alone, on saved forward outputs; h_tgt is cut to
+        # the rows the kernels read, so that the call zero-fills one
+        # [n_src, H, C] arena, not two
+        from glt_amd.ops.segment import _boundaries
+        h, att, tgt, src, n_tgt = inp
+        off = torch.searchsorted(tgt, _boundaries(n_tgt, device))
+        ht = h[:n_tgt]
+        out, m, z, spre = _C.gat_fused_fwd(ht, h, att, att, src, off, 0.2)
+        dout = torch.randn_like(out)
+        fn = lambda: _C.gat_fused_bwd(ht, h, att, att, src, off, out, m, z,
+                                      spre, dout, 0.2)
     elif args.op == "mfma_gemm":
         A, B = inp
         fn = lambda: _C.sage_gemm(A, B, None, False)
