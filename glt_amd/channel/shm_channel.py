@@ -33,7 +33,9 @@ class ShmChannel(ChannelBase):
                 self._queue.pin_memory()
                 self._pinned = True
             except Exception:
-                pass  # no GPU on this box
+                # no GPU on this box, or a host that cannot register
+                # existing pages: the ring stays pageable
+                pass
 
     def send(self, msg: SampleMessage):
         self._queue.send(list(msg.items()))

@@ -7,7 +7,9 @@
  * registered pointers, any pinned/registered host tensor gets a CUDA-device
  * alias tensor (torch::from_blob over hipHostGetDevicePointer) so every
  * kernel and torch op sees an ordinary device tensor whose reads ride UVA
- * over PCIe.
+ * over PCIe.  Where the host cannot register pages it already owns
+ * (hipHostRegister is refused, e.g. on a virtualized GPU) the rows are
+ * staged once into runtime-allocated pinned memory and that copy is mapped.
  */
 #include "hip_common.h"
 #include "../include/common.h"
@@ -43,12 +45,19 @@ torch::Tensor host_mapped_view(const torch::Tensor& src,
   if (!src.is_pinned()) {
     hipError_t e = hipHostRegister(holder->host_ptr, src.nbytes(),
                                    hipHostRegisterMapped);
-    if (e == hipErrorHostMemoryAlreadyRegistered) {
-      (void)hipGetLastError();
-    } else {
-      TORCH_CHECK(e == hipSuccess,
-                  "hipHostRegister failed: ", hipGetErrorString(e));
+    if (e == hipSuccess) {
       holder->registered = true;
+    } else {
+      // a failed call stays behind as the runtime's last error and would be
+      // blamed on the next kernel launch
+      (void)hipGetLastError();
+      if (e != hipErrorHostMemoryAlreadyRegistered) {
+        // Hosts that cannot register existing pages (virtualized GPUs):
+        // stage the rows once into pinned memory the runtime allocates
+        // itself and map that.  The view then no longer aliases `src`.
+        holder->src = src.pin_memory();
+        holder->host_ptr = holder->src.data_ptr();
+      }
     }
   }
   void* dev_ptr = nullptr;
@@ -72,9 +81,10 @@ void pin_host_memory(int64_t addr, int64_t bytes) {
   hipError_t e =
       hipHostRegister(reinterpret_cast<void*>(addr), bytes,
                       hipHostRegisterMapped);
-  if (e == hipErrorHostMemoryAlreadyRegistered) {
+  if (e != hipSuccess) {
+    // do not leave the failure behind for the next kernel launch to report
     (void)hipGetLastError();
-    return;
+    if (e == hipErrorHostMemoryAlreadyRegistered) return;
   }
   TORCH_CHECK(e == hipSuccess, "hipHostRegister: ", hipGetErrorString(e));
   g_pinned[addr] = bytes;

@@ -189,6 +189,20 @@ def test_feature_split_tiers():
     assert torch.equal(out.cpu(), feats[ids])
 
 
+def test_pinning_leaves_no_stale_error():
+    """Whether or not the host can register existing pages, mapping or
+    pinning must not leave a runtime error for the next launch to report."""
+    from glt_amd.channel import ShmChannel
+
+    ch = ShmChannel(4, "1MB")
+    ch.pin_memory()
+    assert torch.ones(8, device="cuda").sum().item() == 8
+    src = torch.arange(64, dtype=torch.float32).view(8, 8)
+    mapped = _C.host_mapped_view(src, 0)
+    assert torch.equal((mapped + 1).cpu(), src + 1)
+    torch.cuda.synchronize()
+
+
 def test_gpu_loader_end_to_end(ring_graph):
     from glt_amd import Dataset, NeighborLoader
 
