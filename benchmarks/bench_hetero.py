@@ -35,6 +35,9 @@ def main():
     # consumer (model step on one cached batch)
     ap.add_argument("--sampler-only", action="store_true")
     ap.add_argument("--model-only", action="store_true")
+    ap.add_argument("--fuse-projections", action="store_true",
+                    help="rsage: one grouped projection GEMM per layer "
+                         "(RGNN(fuse_projections=True))")
     args = ap.parse_args()
 
     import glt_amd
@@ -86,7 +89,8 @@ def main():
         to_device=device, prefetch=args.prefetch if has_gpu else 0)
     model = RGNN(list(ds.graph.keys()), dim, args.hidden, args.classes,
                  num_layers=len(fanout), n_heads=args.heads,
-                 model=args.model).to(device)
+                 model=args.model,
+                 fuse_projections=args.fuse_projections).to(device)
     try:
         opt = torch.optim.Adam(model.parameters(), lr=1e-3, fused=has_gpu)
     except (RuntimeError, ValueError):
@@ -132,7 +136,8 @@ def main():
         "ms_per_step": round(dt / args.steps * 1e3, 3),
         "config": {"dtype": args.dtype, "papers": n_paper, "feat_dim": dim,
                    "fanout": fanout, "batch": args.batch_size,
-                   "model": args.model, "heads": args.heads},
+                   "model": args.model, "heads": args.heads,
+                   "fuse_projections": args.fuse_projections},
     }))
 
 

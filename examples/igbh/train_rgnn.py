@@ -79,6 +79,8 @@ def main():
     ap.add_argument("--steps-per-epoch", type=int, default=50)
     ap.add_argument("--ckpt-dir", type=str, default="")
     ap.add_argument("--ckpt-steps", type=int, default=100)
+    ap.add_argument("--fuse-projections", action="store_true",
+                    help="rsage: one grouped projection GEMM per layer")
     args = ap.parse_args()
 
     has_gpu = torch.cuda.is_available()
@@ -94,7 +96,8 @@ def main():
         to_device=device)
     model = RGNN(list(ds.graph.keys()), args.feat_dim, args.hidden,
                  args.classes, num_layers=len(fanout),
-                 n_heads=args.heads, model=args.model).to(device)
+                 n_heads=args.heads, model=args.model,
+                 fuse_projections=args.fuse_projections).to(device)
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
     step = 0
     if args.ckpt_dir:

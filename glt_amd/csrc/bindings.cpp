@@ -315,6 +315,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_kt_tile_offset", &gemm_kt_tile_offset, py::arg("row"),
         py::arg("chunk"));
   m.def("mfma_bf16_selftest", &hip_mfma_bf16_selftest);
+  m.def("relation_linear_max_segments", &relation_linear_max_segments);
+  m.def("relation_linear_max_groups", &relation_linear_max_groups);
+  m.def("relation_linear_prep", &hip_relation_linear_prep,
+        py::arg("weights"), py::arg("need_t"));
+  m.def("relation_linear_fwd", &hip_relation_linear_fwd, py::arg("xs"),
+        py::arg("w16"), py::arg("biases"), py::arg("group"),
+        py::arg("rows"), py::arg("relu") = false);
+  m.def("relation_linear_mask", &hip_relation_linear_mask, py::arg("dys"),
+        py::arg("ys"));
+  m.def("relation_linear_dgrad", &hip_relation_linear_dgrad, py::arg("dym"),
+        py::arg("wt"), py::arg("group"), py::arg("seg_rows"));
+  m.def("relation_linear_wgrad", &hip_relation_linear_wgrad, py::arg("dym"),
+        py::arg("xs"), py::arg("group"), py::arg("n_out"),
+        py::arg("with_db"));
   m.def("gat_fused_fwd", &hip_gat_fused_fwd);
   m.def("gat_fused_bwd", &hip_gat_fused_bwd);
   m.def("gat_multi_fwd", &hip_gat_multi_fwd);

@@ -290,6 +290,46 @@ int64_t gemm_kt_tile_offset(int64_t row, int64_t chunk);
 torch::Tensor hip_mfma_bf16_selftest(const torch::Tensor& A,
                                      const torch::Tensor& B);
 
+// --- grouped, K-segmented bf16 GEMM (hip_gemm_grouped.hip) -----------------
+// Y_g[i] = act(sum over segments s of g with i < M_s of (x_s[i] @ W_s^T +
+// b_s)): all groups in one launch, fp32 accumulators kept across the
+// segments, one rounding.  Every entry point validates before it launches.
+int64_t relation_linear_max_segments();
+int64_t relation_linear_max_groups();
+// One launch: (W_s as bf16 [N, K_s], W_s^T as bf16 [K_s, Np]) for all s, in
+// one arena; Np = N rounded up to 8, the added columns zero.  A bf16 W_s is
+// returned as it is; the transposes are written only with need_t.
+std::tuple<std::vector<torch::Tensor>, std::vector<torch::Tensor>>
+hip_relation_linear_prep(const std::vector<torch::Tensor>& weights,
+                         bool need_t);
+// xs[s] bf16 [M_s, K_s] (K_s % 8 == 0, dense 16-byte aligned rows), w16[s]
+// bf16 [N_g, K_s], biases[s] fp32 [N_g] or an empty tensor, rows[g] = M_g.
+std::vector<torch::Tensor> hip_relation_linear_fwd(
+    const std::vector<torch::Tensor>& xs,
+    const std::vector<torch::Tensor>& w16,
+    const std::vector<torch::Tensor>& biases,
+    const std::vector<int64_t>& group, const std::vector<int64_t>& rows,
+    bool relu);
+// dY_g -> [M_g, Np], masked where Y_g <= 0 when ys is not empty; a dY that
+// needs neither mask nor padding is returned as it is.
+std::vector<torch::Tensor> hip_relation_linear_mask(
+    const std::vector<torch::Tensor>& dys,
+    const std::vector<torch::Tensor>& ys);
+// dX_s = dYm_g[:seg_rows[s]] @ W_s, through the forward kernel: wt[s] is
+// W_s^T [K_s, Np] from the prep arena.
+std::vector<torch::Tensor> hip_relation_linear_dgrad(
+    const std::vector<torch::Tensor>& dym,
+    const std::vector<torch::Tensor>& wt,
+    const std::vector<int64_t>& group, const std::vector<int64_t>& seg_rows);
+// (dW_s fp32 [N, K_s], db_s fp32 [N] or undefined) for the listed
+// segments: split-K planes and one fold, bit-reproducible.
+std::tuple<std::vector<torch::Tensor>, std::vector<torch::Tensor>>
+hip_relation_linear_wgrad(const std::vector<torch::Tensor>& dym,
+                          const std::vector<torch::Tensor>& xs,
+                          const std::vector<int64_t>& group,
+                          const std::vector<int64_t>& n_out,
+                          const std::vector<bool>& with_db);
+
 // --- memory plumbing (hip_mem.hip) -----------------------------------------
 // Device-dtype alias of (pinned/registered) host memory; keeps `src` alive.
 torch::Tensor host_mapped_view(const torch::Tensor& src, int64_t device_index);

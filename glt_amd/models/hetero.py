@@ -14,10 +14,55 @@ from .layers import GATConv, GATv2Conv, SAGEConv
 class HeteroConv(nn.Module):
     """Applies a per-edge-type conv and sums contributions per dst type."""
 
-    def __init__(self, convs: Dict[EdgeType, nn.Module], aggr: str = "sum"):
+    def __init__(self, convs: Dict[EdgeType, nn.Module], aggr: str = "sum",
+                 fuse_projections: bool = False):
         super().__init__()
         self.convs = nn.ModuleDict({"__".join(k): v for k, v in convs.items()})
         self.aggr = aggr
+        self.fuse_projections = fuse_projections
+
+    def fuses_projections(self) -> bool:
+        """Whether forward_fused applies: the switch is on and every conv
+        is a SAGEConv(root_weight=False)."""
+        return self.fuse_projections and all(
+            isinstance(c, SAGEConv) and not c.root_weight
+            for c in self.convs.values())
+
+    def forward_fused(self, x_dict: Dict[NodeType, torch.Tensor],
+                      edge_index_dict: Dict[EdgeType, torch.Tensor],
+                      self_lins: Dict[NodeType, nn.Module]):
+        """The layer in RGCN form: the per-relation aggregation ops as in
+        forward, then ONE grouped projection (ops.relation_linear) whose
+        groups are the node types of self_lins and whose segments are
+        every relation's aggregate and every type's own features, with
+        bias and ReLU in its epilogue.  Returns relu(conv sum + self
+        projection) per type: what RGNN computes from forward's pair."""
+        from ..ops import relation_linear
+
+        types = [t for t, x in x_dict.items()
+                 if x is not None and t in self_lins]
+        gidx = {t: i for i, t in enumerate(types)}
+        xs, ws, bs, group = [], [], [], []
+        for etype, ei in edge_index_dict.items():
+            key = "__".join(etype)
+            src_t, _, dst_t = etype
+            if key not in self.convs or src_t not in gidx \
+                    or x_dict.get(dst_t) is None:
+                continue
+            conv = self.convs[key]
+            xs.append(conv.aggregate(x_dict[dst_t], ei,
+                                     x_dict[src_t].size(0)))
+            ws.append(conv.lin.weight)
+            bs.append(conv.lin.bias)
+            group.append(gidx[src_t])
+        for t in types:
+            xs.append(x_dict[t])
+            ws.append(self_lins[t].weight)
+            bs.append(self_lins[t].bias)
+            group.append(gidx[t])
+        ys = relation_linear(xs, ws, bs, group,
+                             [x_dict[t].size(0) for t in types], relu=True)
+        return dict(zip(types, ys))
 
     def forward(self, x_dict: Dict[NodeType, torch.Tensor],
                 edge_index_dict: Dict[EdgeType, torch.Tensor],
@@ -264,14 +309,17 @@ class RGNN(nn.Module):
     the layer's output dim even when it receives no messages; ReLU/dropout
     between layers; linear head on the predicted node type.
     sage_aggr ('mean' | 'max' | 'min' | 'sum') is the neighbor aggregator
-    of the 'rsage' convs.
+    of the 'rsage' convs.  fuse_projections (rsage): a layer's relation and
+    self projections, their sum and the ReLU run as one grouped GEMM
+    (HeteroConv.forward_fused); parameters and state_dict are the same in
+    both settings.
     """
 
     def __init__(self, etypes: List[EdgeType], in_dim: int, h_dim: int,
                  out_dim: int, num_layers: int = 2, n_heads: int = 4,
                  model: str = "rgat", dropout: float = 0.2,
                  node_types: Optional[List[NodeType]] = None,
-                 sage_aggr: str = "mean"):
+                 sage_aggr: str = "mean", fuse_projections: bool = False):
         super().__init__()
         self.model = model
         if node_types is None:
@@ -294,7 +342,8 @@ class RGNN(nn.Module):
                     convs[et] = SAGEConv(dims[li], dims[li + 1],
                                          root_weight=False,
                                          aggr=sage_aggr)
-            self.layers.append(HeteroConv(convs))
+            self.layers.append(HeteroConv(
+                convs, fuse_projections=fuse_projections))
             self.self_lins.append(nn.ModuleDict(
                 {t: nn.Linear(dims[li], dims[li + 1])
                  for t in node_types}))
@@ -306,6 +355,11 @@ class RGNN(nn.Module):
                 predict_type: Optional[NodeType] = None):
         h = x_dict
         for i, layer in enumerate(self.layers):
+            if layer.fuses_projections():
+                h = {t: F.dropout(v, p=self.dropout, training=self.training)
+                     for t, v in layer.forward_fused(
+                         h, edge_index_dict, self.self_lins[i]).items()}
+                continue
             h_conv, self_out = layer(h, edge_index_dict,
                                      self_lins=self.self_lins[i])
             h_next = {}

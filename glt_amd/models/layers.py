@@ -89,16 +89,8 @@ class SAGEConv(nn.Module):
                                  "tensor input")
             x_tgt, x_src = x
             n = num_target if num_target is not None else x_tgt.size(0)
-            tgt, src = edge_index[0], edge_index[1]
-            if x_src.is_cuda and sorted_by_target and \
-                    x_src.dtype in (torch.float32, torch.bfloat16):
-                from ..ops import segment_mean
-
-                agg = segment_mean(x_src, tgt, src, n)
-            else:
-                agg = x_src.new_zeros(n, x_src.size(1))
-                agg.index_add_(0, tgt, x_src.index_select(0, src))
-                agg = agg / _degree(tgt, n).unsqueeze(1).to(x_src.dtype)
+            agg = self._mean_bipartite(x_src, edge_index, n,
+                                       sorted_by_target)
             if self.root_weight:
                 xin = torch.cat([agg, x_tgt[:n]], dim=1)
             else:
@@ -127,6 +119,33 @@ class SAGEConv(nn.Module):
             xin = torch.cat([agg, x[:n]], dim=1) if self.root_weight \
                 else agg
         return self._project(xin, fuse_relu, relu_grad_by_consumer)
+
+    @staticmethod
+    def _mean_bipartite(x_src, edge_index, n, sorted_by_target):
+        tgt, src = edge_index[0], edge_index[1]
+        if x_src.is_cuda and sorted_by_target and \
+                x_src.dtype in (torch.float32, torch.bfloat16):
+            from ..ops import segment_mean
+
+            return segment_mean(x_src, tgt, src, n)
+        agg = x_src.new_zeros(n, x_src.size(1))
+        agg.index_add_(0, tgt, x_src.index_select(0, src))
+        return agg / _degree(tgt, n).unsqueeze(1).to(x_src.dtype)
+
+    def aggregate(self, x_src, edge_index, num_target: int,
+                  sorted_by_target: bool = True) -> torch.Tensor:
+        """The neighbour aggregate [num_target, F] alone: what a bipartite
+        forward with root_weight=False projects.  For callers that project
+        several relations in one grouped GEMM (HeteroConv)."""
+        if self.aggr == "mean":
+            return self._mean_bipartite(x_src, edge_index, num_target,
+                                        sorted_by_target)
+        from .. import ops
+
+        op = {"sum": ops.segment_sum, "max": ops.segment_max,
+              "min": ops.segment_min}[self.aggr]
+        return op(x_src, edge_index[0], edge_index[1], num_target,
+                  sorted_by_target)
 
     def takes_relu_input(self, x, sorted_by_target: bool = True) -> bool:
         """Whether forward(x, ...) aggregates through the fused mean

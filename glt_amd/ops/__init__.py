@@ -5,6 +5,7 @@ from .segment import (is_deterministic, segment_max, segment_max_cat,
 from .linear import cast_linear, mfma_linear, use_mfma_linear
 from .gat import (gat_softmax_aggregate, gatv2_composition,
                   gatv2_softmax_aggregate)
+from .relation import relation_linear, relation_linear_uses_kernel
 
 __all__ = ["segment_mean", "segment_mean_cat", "segment_weighted_sum",
            "segment_max", "segment_min", "segment_max_cat",
@@ -12,4 +13,5 @@ __all__ = ["segment_mean", "segment_mean_cat", "segment_weighted_sum",
            "set_deterministic",
            "is_deterministic", "cast_linear",
            "mfma_linear", "use_mfma_linear", "gat_softmax_aggregate",
-           "gatv2_softmax_aggregate", "gatv2_composition"]
+           "gatv2_softmax_aggregate", "gatv2_composition",
+           "relation_linear", "relation_linear_uses_kernel"]

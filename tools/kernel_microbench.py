@@ -265,6 +265,86 @@ def gatv2_table(device, iters, warmup, rounds=5):
                 print(f"gatv2 {name} {label}: "
                       f"{spread([timed(fn) for _ in range(rounds)])}")
 
+# One layer of `bench_hetero.py --model rsage --dtype bf16` (1M papers, batch
+# 512, fanout 10,5, 4 relations; layer 0: K = 128, N = 256): rows per node type and, per
+# segment, (type, rows).  Every relation's aggregate covers all rows of its
+# target type; the last segment of a type is its self projection.
+RSAGE_LAYER_ROWS = {"paper": 26959, "author": 26114, "fos": 18972,
+                    "institute": 7160}
+RSAGE_LAYER_SEGMENTS = [
+    ("paper", 26959), ("paper", 26959), ("paper", 26959), ("paper", 26959),
+    ("author", 26114), ("author", 26114), ("fos", 18972),
+    ("institute", 7160)]
+
+
+def relation_linear_table(device, iters, warmup, rounds=5, K=128, N=256):
+    """--op relation_linear: the grouped projection of one rsage layer
+    (ops.relation_linear, relu=True) against the per-segment composition
+    it replaces (cast_linear per segment, chained adds, F.relu), forward
+    and forward + backward, bf16 inputs over fp32 master weights.  The two
+    are timed alternately, `rounds` times `iters` calls each, from device
+    events; median and range of the rounds, ms per call."""
+    from glt_amd.ops import cast_linear, relation_linear
+
+    def timed(fn):
+        a = torch.cuda.Event(enable_timing=True)
+        b = torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / iters
+
+    def spread(ts):
+        ts = sorted(ts)
+        return "%.3f ms (%.3f - %.3f)" % (ts[len(ts) // 2], ts[0], ts[-1])
+
+    torch.manual_seed(0)
+    types = list(RSAGE_LAYER_ROWS)
+    rows = [RSAGE_LAYER_ROWS[t] for t in types]
+    group = [types.index(t) for t, _ in RSAGE_LAYER_SEGMENTS]
+    xs = [torch.randn(m, K, device=device).to(torch.bfloat16)
+          .requires_grad_(True) for _, m in RSAGE_LAYER_SEGMENTS]
+    ws = [(torch.randn(N, K, device=device) / K ** 0.5).requires_grad_(True)
+          for _ in xs]
+    bs = [torch.randn(N, device=device).requires_grad_(True) for _ in xs]
+    dys = [torch.randn(m, N, device=device).to(torch.bfloat16) for m in rows]
+    print(f"relation_linear shape: K {K}, N {N}, rows {RSAGE_LAYER_ROWS}, "
+          f"{len(xs)} segments")
+
+    def fused():
+        return relation_linear(xs, ws, bs, group, rows, relu=True)
+
+    def composition():
+        out = [None] * len(rows)
+        for x, w, b, g in zip(xs, ws, bs, group):
+            h = cast_linear(x, w, b)
+            out[g] = h if out[g] is None else out[g] + h
+        return [torch.relu(o) for o in out]
+
+    def train(fn):
+        for t in xs + ws + bs:
+            t.grad = None
+        torch.autograd.backward(fn(), dys)
+
+    cases = {"fwd": (lambda: fused(), lambda: composition()),
+             "fwd+bwd": (lambda: train(fused), lambda: train(composition))}
+    for label, (f, c) in cases.items():
+        ctx = torch.no_grad() if label == "fwd" else torch.enable_grad()
+        with ctx:
+            for _ in range(warmup):
+                f()
+                c()
+            tf, tc = [], []
+            for _ in range(rounds):
+                tf.append(timed(f))
+                tc.append(timed(c))
+        print(f"relation_linear bf16 {label}: fused {spread(tf)}, "
+              f"composition {spread(tc)}, ratio of medians "
+              f"{sorted(tc)[rounds // 2] / sorted(tf)[rounds // 2]:.2f}x")
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -278,7 +358,7 @@ def main():
                              "seg_wsum", "seg_wsum_bf16", "gcn_conv",
                              "gcn_conv_composite", "seg_max", "seg_max_cat",
                              "sage_conv_max", "sage_conv_max_composite",
-                             "seg_bwd", "gatv2"])
+                             "seg_bwd", "gatv2", "relation_linear"])
     ap.add_argument("--bf16", action="store_true",
                     help="gcn_conv, seg_mean, seg_max and sage_conv_max "
                          "ops: bf16 input at F=100 (default fp32 at F=256)")
@@ -298,6 +378,9 @@ def main():
         return
     if args.op == "gatv2":
         gatv2_table(device, args.iters, args.warmup)
+        return
+    if args.op == "relation_linear":
+        relation_linear_table(device, args.iters, args.warmup)
         return
     inp = build_flagship_shapes(args.op, device, args.bf16)
 
