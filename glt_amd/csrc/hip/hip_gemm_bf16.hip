@@ -45,15 +45,13 @@
 #include <string>
 
 #include "hip_common.h"
+#include "hip_mfma_tile.h"
 #include "../include/common.h"
 #include "../include/hip_ops.h"
 
 namespace glt {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4b;
 
 constexpr int GBM = 64, GBN = 64, GBK = 64;  // block tile
 constexpr int LDP = 8;                       // LDS row pad (bf16 elems)
@@ -82,7 +80,7 @@ void gemm_bt_kernel(const __bf16* __restrict__ A,
   const int64_t block_row = (int64_t)blockIdx.x * GBM;
   const int64_t block_col = (int64_t)blockIdx.y * GBN;
 
-  f32x4b acc[2][2] = {};
+  f32x4 acc[2][2] = {};
 
   // staging map: 256 threads, each loads 16 bf16 (32 B) per row set;
   // a 64x64 bf16 tile is 256 x 16 elements.
@@ -263,7 +261,7 @@ void gemm_bt_persist_kernel(const __bf16* __restrict__ A,
       }
     }
     __syncthreads();
-    f32x4b acc[2][2] = {};
+    f32x4 acc[2][2] = {};
     for (int kk = 0; kk < kp; kk += 32) {
       bf16x8 a0 = *reinterpret_cast<const bf16x8*>(
           &As[wr * 32 + fi][kk + fk8]);
@@ -317,223 +315,51 @@ void gemm_bt_persist_kernel(const __bf16* __restrict__ A,
 //
 // A and Bt are K-innermost in memory, so a 64-wide K step of either is
 // staged as it is loaded: 16-byte LDS writes of the 16-byte global loads
-// into a [row][64] image with 128-byte rows, XOR-swizzled (bt_tile_off),
+// into a [row][64] image with 128-byte rows, XOR-swizzled (rm_tile_off),
 // and 16-byte fragment reads.  The loads of step i+1 are issued into
 // registers right after the barrier of step i and written to LDS after
-// its MFMAs.  The MFMA, the lane-to-k map (lane group g holds
-// k = kk + 8g .. +7) and the ascending kk order are those of
+// its MFMAs.  The image, the K loop and the line-store epilogue are
+// hip_mfma_tile.h's (rm_*).  The MFMA, the lane-to-k map (lane group g
+// holds k = kk + 8g .. +7) and the ascending kk order are those of
 // gemm_bt_kernel, and a kk step of nothing but zero padding that is
 // skipped here adds +0 there: outputs are bit-for-bit the same.
 // ---------------------------------------------------------------------------
 constexpr int WBN = 256;                   // output columns per workgroup
-constexpr int BT_ROW_BYTES = GBK * 2;      // one staged row: 64 k
-constexpr int BT_EP_LD = 68;               // epilogue row stride in floats
-
-// Byte offset of 16-byte chunk `ch` (0..7: k = 8 ch .. 8 ch + 7) of row
-// `row` in a staged image.  Rows are 128 bytes, so two rows fill the 64
-// banks once; XOR-ing the chunk with bits 1..3 of the row makes the eight
-// rows of one parity in any aligned 16-row block start in eight different
-// 16-byte slots.  The 8 lanes of a 16-byte store group write the 8 chunks
-// of one row (a permutation of the 8 slots), and the 16 lanes of a
-// 16-byte read group, 8 rows at chunk c and 8 at chunk c ^ 1 of one
-// aligned 16-row block, cover all 64 banks exactly once.
-__host__ __device__ constexpr int bt_tile_off(int row, int ch) {
-  return BT_ROW_BYTES * row + 16 * (ch ^ ((row >> 1) & 7));
-}
-
-// This thread's 16-byte chunks of the K step at k0: chunk s_ch of rows
-// row0 + s_row + RPP * h of X[rows, K].  bt_issue only starts the loads,
-// without a branch: a row past `rows` reads the last row and a chunk past
-// K reads chunk 0 (both in bounds: rows >= 1, K >= 32 and K % 8 == 0 on
-// this path, so a chunk is wholly inside K or wholly outside).  bt_finish,
-// at LDS-write time, zeroes what was out of range: the image is
-// zero-padded, never masked.
-template <int NV, int RPP>
-__device__ __forceinline__ void bt_issue(const __bf16* __restrict__ X,
-                                         int64_t rows, int64_t K,
-                                         int64_t row0, int64_t k0, int s_row,
-                                         int s_ch, bf16x8 (&v)[NV]) {
-  const int64_t k = k0 + s_ch * 8;
-  const int64_t kc = k + 8 <= K ? k : 0;
-#pragma unroll
-  for (int h = 0; h < NV; ++h) {
-    const int64_t g_row = std::min<int64_t>(row0 + s_row + RPP * h, rows - 1);
-    v[h] = *reinterpret_cast<const bf16x8*>(&X[g_row * K + kc]);
-  }
-}
-
-template <int NV, int RPP>
-__device__ __forceinline__ void bt_finish(int64_t rows, int64_t K,
-                                          int64_t row0, int64_t k0, int s_row,
-                                          int s_ch, bf16x8 (&v)[NV]) {
-  const bool k_in = k0 + s_ch * 8 + 8 <= K;
-#pragma unroll
-  for (int h = 0; h < NV; ++h)
-    if (!(k_in && row0 + s_row + RPP * h < rows)) v[h] = bf16x8{};
-}
 
 template <int BM, bool RELU, bool BF16_OUT>
-__global__ __launch_bounds__(BM * 4)
+__global__ __launch_bounds__(BM * 4) GLT_NO_PACKED_FP32
 void gemm_bt_wide_kernel(const __bf16* __restrict__ A,
                          const __bf16* __restrict__ Bt,
                          const float* __restrict__ bias,
                          void* __restrict__ Cv,
                          int64_t M, int64_t K, int64_t N, int n_blk) {
-  constexpr int NT = BM * 4;               // threads
-  constexpr int RPP = NT / 8;              // rows one staging pass covers
-  constexpr int NA = BM / RPP, NB = WBN / RPP;
-  static_assert(BM % 64 == 0 && NA >= 1, "whole 64-row wave tiles");
+  static_assert(BM % 64 == 0, "whole 64-row wave tiles");
   // A image, then the Bt image; the epilogue reuses the front of it
-  alignas(16) __shared__ unsigned char smem[(BM + WBN) * BT_ROW_BYTES];
-  static_assert((NT / 64) * 16 * BT_EP_LD * 4 <= (BM + WBN) * BT_ROW_BYTES,
-                "epilogue tiles fit in the staging buffers");
-  unsigned char* const As = smem;
-  unsigned char* const Bs = smem + BM * BT_ROW_BYTES;
+  alignas(16) __shared__ unsigned char smem[(BM + WBN) * RM_ROW_BYTES];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
   const int wm = wave >> 2;                // 64-row wave tile
   const int wn = wave & 3;                 // 64-col wave tile
-
   const int64_t block_col = (int64_t)(blockIdx.x % n_blk) * WBN;
   const int64_t block_row = (int64_t)(blockIdx.x / n_blk) * BM;
-  // a wave whose 64 columns all lie past N multiplies nothing
-  const bool live = block_col + wn * 64 < N;
 
-  f32x4b acc[4][4] = {};
+  f32x4 acc[4][4] = {};
+  rm_k_loop<BM, WBN, 4, 4>(smem, A, K, M, Bt, N, K, block_row, block_col,
+                           acc);
 
-  // staging: 8 lanes take the 8 chunks of one row
-  const int s_row = tid >> 3;
-  const int s_ch = tid & 7;
-  const int fi = lane & 15;                // fragment row / col
-  const int fg = lane >> 4;                // fragment k group
-
-  bf16x8 va[NA], vb[NB];
-  if (K > 0) {
-    bt_issue<NA, RPP>(A, M, K, block_row, 0, s_row, s_ch, va);
-    bt_issue<NB, RPP>(Bt, N, K, block_col, 0, s_row, s_ch, vb);
-  }
-
-  for (int64_t k0 = 0; k0 < K; k0 += GBK) {
-    bt_finish<NA, RPP>(M, K, block_row, k0, s_row, s_ch, va);
-    bt_finish<NB, RPP>(N, K, block_col, k0, s_row, s_ch, vb);
-#pragma unroll
-    for (int h = 0; h < NA; ++h)
-      *reinterpret_cast<bf16x8*>(
-          As + bt_tile_off(s_row + RPP * h, s_ch)) = va[h];
-#pragma unroll
-    for (int h = 0; h < NB; ++h)
-      *reinterpret_cast<bf16x8*>(
-          Bs + bt_tile_off(s_row + RPP * h, s_ch)) = vb[h];
-    __syncthreads();
-    if (k0 + GBK < K) {
-      bt_issue<NA, RPP>(A, M, K, block_row, k0 + GBK, s_row, s_ch, va);
-      bt_issue<NB, RPP>(Bt, N, K, block_col, k0 + GBK, s_row, s_ch, vb);
-    }
-
-#pragma unroll
-    for (int kk = 0; kk < GBK; kk += 32) {
-      // a kk step past K holds only zero padding
-      if (live && k0 + kk < K) {
-        bf16x8 a[4], b[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          a[i] = *reinterpret_cast<const bf16x8*>(
-              As + bt_tile_off(wm * 64 + i * 16 + fi, (kk >> 3) + fg));
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          b[j] = *reinterpret_cast<const bf16x8*>(
-              Bs + bt_tile_off(wn * 64 + j * 16 + fi, (kk >> 3) + fg));
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                a[i], b[j], acc[i][j], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-
-  // Epilogue.  C/D: col = lane & 15, row = (lane >> 4) * 4 + reg.  Bias
-  // and ReLU in fp32 as in gemm_bt_kernel, then each wave passes its
-  // 64x64 tile, 16 rows at a time, through its own [16][68] fp32 LDS tile
-  // (the staging buffers: every wave is past the last barrier above) and
-  // writes whole row pieces, 16 bytes per lane: 8 lanes a 128-byte row
-  // piece of bf16 (rounded once, here), 16 lanes 256 bytes of fp32.  The
-  // 68-float stride puts the two rows a 32-lane half writes 16 banks
-  // apart.  A row of C starts 16-byte aligned only if N is a multiple of
-  // 8 (bf16) or 4 (fp32); otherwise, and in the N tail, elements are
-  // stored one by one.
-  float* const ep = reinterpret_cast<float*>(smem) + wave * (16 * BT_EP_LD);
+  // bias in fp32, as in gemm_bt_kernel, before ReLU and the one rounding
   float bv[4] = {0.f, 0.f, 0.f, 0.f};
   if (bias != nullptr) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int64_t col = block_col + wn * 64 + j * 16 + fi;
+      const int64_t col = block_col + wn * 64 + j * 16 + (lane & 15);
       if (col < N) bv[j] = bias[col];
     }
   }
-  constexpr int CPL = BF16_OUT ? 8 : 4;    // columns per lane
-  constexpr int LPR = 64 / CPL;            // lanes per 64-column row piece
-  constexpr int RPI = 64 / LPR;            // rows per wave instruction
-  const bool vec_ok = N % CPL == 0;
-  const int e_row = lane / LPR;
-  const int e_col = (lane % LPR) * CPL;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = acc[i][j][r];
-        if (bias != nullptr) v += bv[j];
-        if (RELU) v = v > 0.f ? v : 0.f;
-        ep[(fg * 4 + r) * BT_EP_LD + j * 16 + fi] = v;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 16 / RPI; ++h) {
-      const int rr = e_row + RPI * h;
-      const int64_t row = block_row + wm * 64 + i * 16 + rr;
-      const int64_t col = block_col + wn * 64 + e_col;
-      const float* src = ep + rr * BT_EP_LD + e_col;
-      const f32x4b lo = *reinterpret_cast<const f32x4b*>(src);
-      if (BF16_OUT) {
-        const f32x4b hi = *reinterpret_cast<const f32x4b*>(src + 4);
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          o[e] = f2bf(lo[e]);
-          o[4 + e] = f2bf(hi[e]);
-        }
-        __bf16* dst = reinterpret_cast<__bf16*>(Cv) + row * N + col;
-        if (row < M) {
-          if (vec_ok && col + 7 < N) {
-            *reinterpret_cast<bf16x8*>(dst) = o;
-          } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-              if (col + e < N) dst[e] = o[e];
-          }
-        }
-      } else {
-        float* dst = reinterpret_cast<float*>(Cv) + row * N + col;
-        if (row < M) {
-          if (vec_ok && col + 3 < N) {
-            *reinterpret_cast<f32x4b*>(dst) = lo;
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (col + e < N) dst[e] = lo[e];
-          }
-        }
-      }
-    }
-    __syncthreads();
-  }
+  rm_store_lines<4, 4, BF16_OUT>(smem, acc, bv, bias != nullptr, RELU, Cv,
+                                 M, N, block_row + wm * 64,
+                                 block_col + wn * 64);
 }
 
 // ---------------------------------------------------------------------------
@@ -566,7 +392,7 @@ void gemm_kt_kernel(const __bf16* __restrict__ A,
   const int64_t kz0 = (int64_t)blockIdx.z * k_per_z;
   const int64_t kz1 = std::min(kz0 + k_per_z, Kb);
 
-  f32x4b acc[2][2] = {};
+  f32x4 acc[2][2] = {};
 
   // transposing stage: thread owns TWO adjacent k rows x 8 cols, so
   // each LDS write is a b32 pair (halves the transpose instruction
@@ -705,197 +531,42 @@ void gemm_kt_kernel(const __bf16* __restrict__ A,
 // index), so a 64 x 128 K-step tile is staged exactly as it is loaded:
 // 16-byte LDS writes of the 16-byte global loads into a [k][128] image
 // with 256-byte rows, and ds_read_b64_tr_b16 turns 4-row x 16-column
-// blocks of it into MFMA fragments.  No transposing write pass.
+// blocks of it into MFMA fragments.  No transposing write pass.  The image,
+// the K loop and the plane store are hip_mfma_tile.h's (km_*); the kernel
+// decodes its 3-D grid and says where its plane lives.  Neither operand is
+// padded, so a tile over the edge of a width that is no multiple of 8 has
+// one chunk per row that straddles it.
 // ---------------------------------------------------------------------------
-constexpr int KBM = 128, KBN = 128;
-constexpr int KT_ROW_BYTES = KBM * 2;          // one k row of the image
-constexpr int KT_TILE_BYTES = GBK * KT_ROW_BYTES;
-static_assert(KBM == KBN, "A and B share one image geometry");
-
-// Byte offset of 16-byte chunk `ch` (0..15) of k row `row` (0..63) in the
-// tile image.  The XOR spreads both the 8-lane groups of a 16-byte store
-// and the two 4-row blocks a 32-lane half reads transposed over all banks;
-// stores and reads go through this one function.
-__host__ __device__ constexpr int kt_tile_off(int row, int ch) {
-  return KT_ROW_BYTES * row +
-         16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
-
-typedef __attribute__((ext_vector_type(4))) short i16x4;
-typedef __attribute__((ext_vector_type(8))) short i16x8;
-
-// 16x16x32 operand fragment for columns 8*c0 .. 8*c0+15 (c0 even) and
-// k rows r0 .. r0+7 of this lane's 16-lane group: lane (fi, g) ends up
-// with column fi, rows r0 + 0..7 in elements 0..7.  Each transposed read
-// takes a 4-row block; lane 4q+p of the group addresses row q, elements
-// 4p .. 4p+3 of the block.  Every lane of the wave must be active here.
-__device__ __forceinline__ bf16x8 kt_frag(const unsigned char* tile, int r0,
-                                          int c0, int lane) {
-  const int q = (lane & 15) >> 2, p = lane & 3;
-  typedef __attribute__((address_space(3))) i16x4* lds_i16x4;
-  const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4)(
-      tile + kt_tile_off(r0 + q, c0 + (p >> 1)) + 8 * (p & 1)));
-  const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4)(
-      tile + kt_tile_off(r0 + 4 + q, c0 + (p >> 1)) + 8 * (p & 1)));
-  return __builtin_bit_cast(
-      bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
-// This thread's two 16-byte chunks of the K step at k0: rows
-// k0 + s_row + {0, 32}, columns col0 .. col0+7 of X[Kb, ld].  kt_issue
-// only starts the loads, without a branch, so that nothing waits for them
-// before the MFMAs: a row past kz1 reads row kz1-1 and a chunk that is
-// not wholly inside ld reads columns 0..7 instead (both in bounds: the
-// chunk is not empty and ld >= 8 on this path).  kt_finish, at LDS-write
-// time, zeroes what was out of range (the image is zero-padded, never
-// masked) and fetches a chunk that straddles ld element by element;
-// `straddle` is block-uniform and false whenever ld is a multiple of 8.
-__device__ __forceinline__ void kt_issue(const __bf16* __restrict__ X,
-                                         int64_t ld, int64_t col0,
-                                         int64_t k0, int64_t kz1, int s_row,
-                                         bf16x8 (&v)[2]) {
-  const int64_t c = col0 + 7 < ld ? col0 : 0;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int64_t g_k = std::min<int64_t>(k0 + s_row + 32 * h, kz1 - 1);
-    v[h] = *reinterpret_cast<const bf16x8*>(&X[g_k * ld + c]);
-  }
-}
-
-__device__ __forceinline__ void kt_finish(const __bf16* __restrict__ X,
-                                          int64_t ld, int64_t col0,
-                                          int64_t k0, int64_t kz1, int s_row,
-                                          bool straddle, bf16x8 (&v)[2]) {
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int64_t g_k = k0 + s_row + 32 * h;
-    if (!(g_k < kz1 && col0 + 7 < ld)) v[h] = bf16x8{};
-  }
-  if (straddle) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int64_t g_k = k0 + s_row + 32 * h;
-      if (g_k < kz1 && col0 < ld && col0 + 7 >= ld) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (col0 + e < ld) v[h][e] = X[g_k * ld + col0 + e];
-      }
-    }
-  }
-}
+constexpr int KBM = KM_BT, KBN = KM_BT;
 
 template <bool WITH_DB>
-__global__ __launch_bounds__(512)
+__global__ __launch_bounds__(512) GLT_NO_PACKED_FP32
 void gemm_kt128_kernel(const __bf16* __restrict__ A,
                        const __bf16* __restrict__ B,
                        float* __restrict__ C,
                        float* __restrict__ db,
                        int64_t Kb, int64_t M, int64_t N,
                        int64_t k_per_z, int64_t plane) {
-  alignas(16) __shared__ unsigned char As[KT_TILE_BYTES];   // [k][m]
-  alignas(16) __shared__ unsigned char Bs[KT_TILE_BYTES];   // [k][n]
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;               // 0..7
-  const int wm = wave >> 2;                // 0..1 (64 rows each)
-  const int wn = wave & 3;                 // 0..3 (32 cols each)
+  alignas(16) __shared__ unsigned char As[KM_TILE_BYTES];   // [k][m]
+  alignas(16) __shared__ unsigned char Bs[KM_TILE_BYTES];   // [k][n]
+  __shared__ float dbs[KBM][4];
 
   const int64_t block_row = (int64_t)blockIdx.x * KBM;
   const int64_t block_col = (int64_t)blockIdx.y * KBN;
   const int64_t kz0 = (int64_t)blockIdx.z * k_per_z;
-  const int64_t kz1 = std::min(kz0 + k_per_z, Kb);
-
-  f32x4b acc[4][2] = {};
-
-  // staging: 512 threads = 32 k rows x 16 chunks, two row sets per tile
-  const int s_row = tid >> 4;              // 0..31 (+32)
-  const int s_ch = tid & 15;               // 16-byte chunk of the row
-
-  const int fg8 = (lane >> 4) * 8;         // fragment k base
-
-  // db: thread (m_l, phase) sums rows phase, phase+4, ... of column m_l
-  const int m_l = tid & 127, phase = tid >> 7;
+  const int64_t kz1 = kz0 + k_per_z < Kb ? kz0 + k_per_z : Kb;
   const bool do_db = WITH_DB && blockIdx.y == 0;
-  float s = 0.f;
-
-  // the next K step's loads are in flight in registers during the MFMAs
-  const int64_t a_col = block_row + s_ch * 8, b_col = block_col + s_ch * 8;
   const bool a_straddle = (M & 7) != 0 && block_row + KBM > M;
   const bool b_straddle = (N & 7) != 0 && block_col + KBN > N;
-  bf16x8 va[2], vb[2];
-  if (kz0 < kz1) {
-    kt_issue(A, M, a_col, kz0, kz1, s_row, va);
-    kt_issue(B, N, b_col, kz0, kz1, s_row, vb);
-  }
 
-  for (int64_t k0 = kz0; k0 < kz1; k0 += GBK) {
-    kt_finish(A, M, a_col, k0, kz1, s_row, a_straddle, va);
-    kt_finish(B, N, b_col, k0, kz1, s_row, b_straddle, vb);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      *reinterpret_cast<bf16x8*>(
-          As + kt_tile_off(s_row + 32 * h, s_ch)) = va[h];
-      *reinterpret_cast<bf16x8*>(
-          Bs + kt_tile_off(s_row + 32 * h, s_ch)) = vb[h];
-    }
-    __syncthreads();
-    if (k0 + GBK < kz1) {
-      kt_issue(A, M, a_col, k0 + GBK, kz1, s_row, va);
-      kt_issue(B, N, b_col, k0 + GBK, kz1, s_row, vb);
-    }
-
-#pragma unroll
-    for (int kk = 0; kk < GBK; kk += 32) {
-      bf16x8 a[4], b[2];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        a[i] = kt_frag(As, kk + fg8, wm * 8 + i * 2, lane);
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        b[j] = kt_frag(Bs, kk + fg8, wn * 4 + j * 2, lane);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-    if (do_db) {
-      // from the staged tile, in ascending k; the zero rows past kz1 add
-      // +0 to a sum that is never -0, so the result is that of the
-      // bounded loop
-#pragma unroll
-      for (int r = 0; r < GBK; r += 4)
-        s += bf2f(*reinterpret_cast<const __bf16*>(
-            As + kt_tile_off(r + phase, m_l >> 3) + 2 * (m_l & 7)));
-    }
-    __syncthreads();
-  }
-
-  const int c_col = lane & 15;
-  const int c_row0 = (lane >> 4) * 4;
-  float* Cz = C + (int64_t)blockIdx.z * plane;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t row = block_row + wm * 64 + i * 16 + c_row0 + r;
-        const int64_t col = block_col + wn * 32 + j * 16 + c_col;
-        if (row < M && col < N) Cz[row * N + col] = acc[i][j][r];
-      }
-    }
-  }
-  if (do_db) {
-    __shared__ float dbs[KBM][4];
-    dbs[m_l][phase] = s;
-    __syncthreads();
-    if (tid < KBM && block_row + tid < M)
-      db[(int64_t)blockIdx.z * plane + block_row + tid] =
-          dbs[tid][0] + dbs[tid][1] + dbs[tid][2] + dbs[tid][3];
-  }
+  f32x4 acc[4][2] = {};
+  float dsum = 0.f;
+  km_k_loop(As, Bs, A, M, M, a_straddle, B, N, N, b_straddle, block_row,
+            block_col, kz0, kz1, do_db, acc, dsum);
+  // the chunk's db row follows its C in the plane (db = C + M * N)
+  km_store_plane(C + (int64_t)blockIdx.z * plane,
+                 WITH_DB ? db + (int64_t)blockIdx.z * plane : nullptr, dbs,
+                 M, N, block_row, block_col, acc, do_db, dsum);
 }
 
 // ---------------------------------------------------------------------------
@@ -910,7 +581,7 @@ __global__ void selftest_16x16x32(const __bf16* A, const __bf16* B,
     af[e] = A[(lane & 15) * 32 + (lane >> 4) * 8 + e];       // A[i][k]
     bf_[e] = B[((lane >> 4) * 8 + e) * 16 + (lane & 15)];    // B[k][j]
   }
-  f32x4b acc = {};
+  f32x4 acc = {};
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf_, acc, 0, 0, 0);
 #pragma unroll
   for (int r = 0; r < 4; ++r)
@@ -965,13 +636,14 @@ GemmBtPlan gemm_bt_bf16_plan(int64_t M, int64_t K, int64_t N, bool aligned) {
   return p;
 }
 
-// Byte offset of 16-byte chunk `chunk` of row `row` in the wide kernel's
-// staged [rows][64] bf16 LDS images (A: 64 rows, Bt: 256 rows; one
-// function for both, the one the kernel stores and reads through).
+// Byte offset of 16-byte chunk `chunk` of row `row` in a staged [rows][64]
+// bf16 LDS image: rm_tile_off, the one function gemm_bt_wide_kernel (A: 64
+// rows, Bt: 256) and relation_gemm_kernel (A: 64 rows, W: 128) store and
+// read through.
 int64_t gemm_bt_tile_offset(int64_t row, int64_t chunk) {
-  TORCH_CHECK(row >= 0 && row < WBN && chunk >= 0 && chunk < GBK / 8,
+  TORCH_CHECK(row >= 0 && row < WBN && chunk >= 0 && chunk < MT_BK / 8,
               "row in [0, 256) and chunk in [0, 8) required");
-  return bt_tile_off((int)row, (int)chunk);
+  return rm_tile_off((int)row, (int)chunk);
 }
 
 // C = act(A @ Bt^T + bias): A [M,K] bf16, Bt [N,K] bf16 (nn.Linear
@@ -1082,13 +754,14 @@ GemmKtPlan gemm_kt_bf16_plan(int64_t Kb, int64_t M, int64_t N) {
   return p;
 }
 
-// Byte offset of 16-byte chunk `chunk` of k row `row` in the 128x128
-// kernel's [64][128] bf16 LDS tile image (the function the kernel stores
-// and reads through; the tests check the layout with it, without a GPU).
+// Byte offset of 16-byte chunk `chunk` of k row `row` in a [64][128] bf16
+// LDS tile image: km_tile_off, the one function gemm_kt128_kernel and
+// relation_wgrad_kernel store and read through (the tests check the layout
+// with it, without a GPU).
 int64_t gemm_kt_tile_offset(int64_t row, int64_t chunk) {
-  TORCH_CHECK(row >= 0 && row < GBK && chunk >= 0 && chunk < KBM / 8,
+  TORCH_CHECK(row >= 0 && row < MT_BK && chunk >= 0 && chunk < KM_BT / 8,
               "row in [0, 64) and chunk in [0, 16) required");
-  return kt_tile_off((int)row, (int)chunk);
+  return km_tile_off((int)row, (int)chunk);
 }
 
 // (dW, db) = (A^T @ B, colsum(A)): A [Kb,M] bf16, B [Kb,N] bf16;

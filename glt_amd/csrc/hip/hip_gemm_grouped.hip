@@ -35,41 +35,34 @@
  * small types twice the workgroups of a 256-wide tile and 24 KB of LDS let
  * six workgroups share a CU, while an A row tile is still read only N/128
  * times, by neighbouring workgroups (the column tile runs fastest).
- * Operands are K-innermost in memory and staged as loaded: 16-byte LDS
- * writes into an XOR-swizzled [row][64] image, the next K step prefetched
- * into registers across the MFMAs without a branch around the loads, zero
- * padding instead of masked lanes, and line-wide epilogue stores.
+ * The staged LDS images, the prefetching K loops and the store epilogues
+ * of 2. and 4. are those of the dense wide kernels (hip_mfma_tile.h).
  */
 #include <algorithm>
 #include <vector>
 
 #include "hip_common.h"
+#include "hip_mfma_tile.h"
 #include "../include/hip_ops.h"
 
 // No packed fp32 arithmetic in this file's device code (the build has one
 // flag set for all files, so the target feature is switched off here).
+// hip_mfma_tile.h opens a scope of this same pragma around its functions,
+// so they and the kernels they are inlined into have one feature set.
 #if defined(__HIP_DEVICE_COMPILE__)
-#pragma clang attribute push(                                            \
-    __attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#pragma clang attribute push(GLT_NO_PACKED_FP32, apply_to = function)
 #endif
 
 namespace glt {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4g;
-typedef __attribute__((ext_vector_type(4))) short i16x4;
-
 // Pack limits: descriptors are kernel arguments (4 KB budget).  The IGBH
 // layer is 4 groups and 11 segments; its input gradient is 11 groups.
 constexpr int kMaxSeg = 16;
 constexpr int kMaxGrp = 16;
 
-constexpr int RBM = 64, RBN = 128, RBK = 64;   // forward tile, K step
-constexpr int R_ROW_BYTES = RBK * 2;           // one staged row: 64 k
-constexpr int R_EP_LD = 68;                    // epilogue row stride, floats
-constexpr int R_RPP = 32;                      // rows per staging pass
+constexpr int RBM = 64, RBN = 128;             // forward tile
 
 struct RlSeg {
   const __bf16* A;      // [M, K], row stride lda
@@ -93,59 +86,17 @@ struct RlPack {
 };
 static_assert(sizeof(RlPack) <= 2048, "kernel-argument budget");
 
-// Byte offset of 16-byte chunk `ch` (k = 8 ch .. 8 ch + 7) of row `row` in
-// a staged image.  Rows are 128 bytes; XOR-ing the chunk with bits 1..3 of
-// the row spreads the 8 lanes of a 16-byte store group (8 chunks of one
-// row) and the 16 lanes of a fragment read group (16 rows at chunks c and
-// c ^ 1) over all 64 banks.
-__device__ __forceinline__ int rl_tile_off(int row, int ch) {
-  return R_ROW_BYTES * row + 16 * (ch ^ ((row >> 1) & 7));
-}
-
-// This thread's 16-byte chunks of the K step at k0: chunk s_ch of rows
-// row0 + s_row + 32 h of X[rows, K] (row stride ld).  rl_issue starts the
-// loads without a branch: a row past `rows` reads the last row and a chunk
-// past K reads chunk 0 (in bounds: rows >= 1, K >= 8, K % 8 == 0).
-// rl_finish, at LDS-write time, zeroes what was out of range.
-template <int NV>
-__device__ __forceinline__ void rl_issue(const __bf16* __restrict__ X,
-                                         int rows, int K, int64_t ld,
-                                         int row0, int k0, int s_row,
-                                         int s_ch, bf16x8 (&v)[NV]) {
-  const int k = k0 + s_ch * 8;
-  const int kc = k + 8 <= K ? k : 0;
-#pragma unroll
-  for (int h = 0; h < NV; ++h) {
-    const int g_row = min(row0 + s_row + R_RPP * h, rows - 1);
-    v[h] = *reinterpret_cast<const bf16x8*>(&X[(int64_t)g_row * ld + kc]);
-  }
-}
-
-template <int NV>
-__device__ __forceinline__ void rl_finish(int rows, int K, int row0, int k0,
-                                          int s_row, int s_ch,
-                                          bf16x8 (&v)[NV]) {
-  const bool k_in = k0 + s_ch * 8 + 8 <= K;
-#pragma unroll
-  for (int h = 0; h < NV; ++h)
-    if (!(k_in && row0 + s_row + R_RPP * h < rows)) v[h] = bf16x8{};
-}
-
 __global__ __launch_bounds__(256)
 void relation_gemm_kernel(const RlPack P) {
-  constexpr int NA = RBM / R_RPP, NB = RBN / R_RPP;
   // A image, then the W image; the epilogue reuses the front
-  alignas(16) __shared__ unsigned char smem[(RBM + RBN) * R_ROW_BYTES];
-  static_assert(4 * 16 * R_EP_LD * 4 <= (RBM + RBN) * R_ROW_BYTES,
-                "epilogue tiles fit in the staging buffers");
-  unsigned char* const As = smem;
-  unsigned char* const Bs = smem + RBM * R_ROW_BYTES;
+  alignas(16) __shared__ unsigned char smem[(RBM + RBN) * RM_ROW_BYTES];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
   const int wm = wave >> 1;                // 32-row wave tile
   const int wn = wave & 1;                 // 64-column wave tile
+  const int fi = lane & 15;                // fragment col
+  const int fg = lane >> 4;                // fragment row group
 
   // work decode: blockIdx is uniform, readfirstlane tells the compiler
   const int wg = (int)blockIdx.x;
@@ -157,77 +108,21 @@ void relation_gemm_kernel(const RlPack P) {
   const int N = G.N, Mg = G.M;
   const int block_col = (local % G.n_blk) * RBN;   // column tile fastest
   const int block_row = (local / G.n_blk) * RBM;
-  // a wave whose 64 columns all lie past N multiplies nothing
-  const bool live = block_col + wn * 64 < N;
 
-  f32x4g acc[2][4] = {};
+  f32x4 acc[2][4] = {};
 
-  const int s_row = tid >> 3;              // 8 lanes take one row's chunks
-  const int s_ch = tid & 7;
-  const int fi = lane & 15;                // fragment row / col
-  const int fg = lane >> 4;                // fragment k group
-
-  // Segment loop outermost: the accumulators live across it.
+  // Segment loop outermost: the accumulators live across it.  A row tile
+  // wholly beyond the segment's rows takes nothing from it; the rows of a
+  // partly covered tile beyond M_s are staged as zeros.
   for (int s = G.seg0; s < G.seg1; ++s) {
     const RlSeg& S = P.seg[s];
-    const int Ms = S.M, K = S.K;
-    // a row tile wholly beyond the segment's rows takes nothing from it
-    if (block_row >= Ms || K <= 0) continue;
-    const __bf16* __restrict__ A = S.A;
-    const __bf16* __restrict__ W = S.W;
-    const int64_t lda = S.lda;
-
-    bf16x8 va[NA], vb[NB];
-    rl_issue<NA>(A, Ms, K, lda, block_row, 0, s_row, s_ch, va);
-    rl_issue<NB>(W, N, K, K, block_col, 0, s_row, s_ch, vb);
-
-    for (int k0 = 0; k0 < K; k0 += RBK) {
-      // rows of a partly covered tile beyond Ms are staged as zeros
-      rl_finish<NA>(Ms, K, block_row, k0, s_row, s_ch, va);
-      rl_finish<NB>(N, K, block_col, k0, s_row, s_ch, vb);
-#pragma unroll
-      for (int h = 0; h < NA; ++h)
-        *reinterpret_cast<bf16x8*>(
-            As + rl_tile_off(s_row + R_RPP * h, s_ch)) = va[h];
-#pragma unroll
-      for (int h = 0; h < NB; ++h)
-        *reinterpret_cast<bf16x8*>(
-            Bs + rl_tile_off(s_row + R_RPP * h, s_ch)) = vb[h];
-      __syncthreads();
-      if (k0 + RBK < K) {
-        rl_issue<NA>(A, Ms, K, lda, block_row, k0 + RBK, s_row, s_ch, va);
-        rl_issue<NB>(W, N, K, K, block_col, k0 + RBK, s_row, s_ch, vb);
-      }
-#pragma unroll
-      for (int kk = 0; kk < RBK; kk += 32) {
-        // a kk step past K holds only zero padding
-        if (live && k0 + kk < K) {
-          bf16x8 a[2], b[4];
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-            a[i] = *reinterpret_cast<const bf16x8*>(
-                As + rl_tile_off(wm * 32 + i * 16 + fi, (kk >> 3) + fg));
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            b[j] = *reinterpret_cast<const bf16x8*>(
-                Bs + rl_tile_off(wn * 64 + j * 16 + fi, (kk >> 3) + fg));
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                  a[i], b[j], acc[i][j], 0, 0, 0);
-        }
-      }
-      __syncthreads();
-    }
+    if (block_row >= S.M) continue;
+    rm_k_loop<RBM, RBN, 2, 4>(smem, S.A, S.lda, S.M, S.W, N, S.K, block_row,
+                              block_col, acc);
   }
 
-  // Epilogue.  Biases in segment order, in fp32, on the rows their segment
-  // covers; ReLU; then each wave passes its 32x64 tile, 16 rows at a time,
-  // through its own [16][68] fp32 LDS tile and writes 128-byte row pieces,
-  // 16 bytes per lane, rounded once here.  Rows of C start 16-byte aligned
-  // only if N % 8 == 0; otherwise, and in the N tail, element stores.
+  // Biases in segment order, in fp32, on the rows their segment covers;
+  // then ReLU, the one rounding and the line stores.
   for (int s = G.seg0; s < G.seg1; ++s) {
     const float* __restrict__ bias = P.seg[s].bias;
     if (bias == nullptr) continue;
@@ -247,50 +142,9 @@ void relation_gemm_kernel(const RlPack P) {
           for (int j = 0; j < 4; ++j) acc[i][j][r] += bv[j];
         }
   }
-  float* const ep = reinterpret_cast<float*>(smem) + wave * (16 * R_EP_LD);
-  const bool relu = P.relu != 0;
-  const bool vec_ok = N % 8 == 0;
-  const int e_row = lane >> 3;
-  const int e_col = (lane & 7) * 8;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = acc[i][j][r];
-        if (relu) v = v > 0.f ? v : 0.f;
-        ep[(fg * 4 + r) * R_EP_LD + j * 16 + fi] = v;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int rr = e_row + 8 * h;
-      const int row = block_row + wm * 32 + i * 16 + rr;
-      const int col = block_col + wn * 64 + e_col;
-      const float* src = ep + rr * R_EP_LD + e_col;
-      const f32x4g lo = *reinterpret_cast<const f32x4g*>(src);
-      const f32x4g hi = *reinterpret_cast<const f32x4g*>(src + 4);
-      bf16x8 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        o[e] = (__bf16)lo[e];
-        o[4 + e] = (__bf16)hi[e];
-      }
-      if (row < Mg && col < N) {
-        __bf16* dst = G.C + (int64_t)row * N + col;
-        if (vec_ok && col + 7 < N) {
-          *reinterpret_cast<bf16x8*>(dst) = o;
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            if (col + e < N) dst[e] = o[e];
-        }
-      }
-    }
-    __syncthreads();
-  }
+  const float none[4] = {};
+  rm_store_lines<2, 4, true>(smem, acc, none, false, P.relu != 0, G.C, Mg, N,
+                             block_row + wm * 32, block_col + wn * 64);
 }
 
 // ---------------------------------------------------------------------------
@@ -386,9 +240,6 @@ void relation_mask_kernel(const RmPack P) {
 // m tile) also sums db from the staged A tile.  Chunk partials go to
 // planes [M * N + M] of the segment's arena slice.
 // ---------------------------------------------------------------------------
-constexpr int WBT = 128;                       // tile edge
-constexpr int W_ROW_BYTES = WBT * 2;
-
 struct RwSeg {
   const __bf16* A;
   const __bf16* B;
@@ -406,65 +257,11 @@ struct RwPack {
 };
 static_assert(sizeof(RwPack) <= 2048, "kernel-argument budget");
 
-// Byte offset of 16-byte chunk `ch` (0..15) of k row `row` (0..63).  The
-// XOR spreads the 8-lane groups of a 16-byte store and the two 4-row
-// blocks a 32-lane half reads transposed over all banks.
-__device__ __forceinline__ int rw_tile_off(int row, int ch) {
-  return W_ROW_BYTES * row +
-         16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
-
-// 16x16x32 operand fragment for columns 8 c0 .. 8 c0 + 15 (c0 even) and k
-// rows r0 .. r0 + 7: lane (fi, g) ends with column fi, rows r0 + 0..7.
-// Each transposed read takes a 4-row block; lane 4q + p of a 16-lane group
-// addresses row q, elements 4p .. 4p + 3.  All lanes must be active.
-__device__ __forceinline__ bf16x8 rw_frag(const unsigned char* tile, int r0,
-                                          int c0, int lane) {
-  const int q = (lane & 15) >> 2, p = lane & 3;
-  typedef __attribute__((address_space(3))) i16x4* lds_i16x4;
-  const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4)(
-      tile + rw_tile_off(r0 + q, c0 + (p >> 1)) + 8 * (p & 1)));
-  const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4)(
-      tile + rw_tile_off(r0 + 4 + q, c0 + (p >> 1)) + 8 * (p & 1)));
-  return __builtin_bit_cast(
-      bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
-// Rows k0 + s_row + {0, 32}, columns col0 .. col0 + 7 of X[., cols] (row
-// stride ld; cols a multiple of 8, so a chunk is wholly in or out).  The
-// loads start without a branch (a row past kz1 reads row kz1 - 1, a chunk
-// past cols reads columns 0..7); rw_finish zeroes what was out of range.
-__device__ __forceinline__ void rw_issue(const __bf16* __restrict__ X,
-                                         int64_t ld, int cols, int col0,
-                                         int k0, int kz1, int s_row,
-                                         bf16x8 (&v)[2]) {
-  const int c = col0 + 8 <= cols ? col0 : 0;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int g_k = min(k0 + s_row + 32 * h, kz1 - 1);
-    v[h] = *reinterpret_cast<const bf16x8*>(&X[(int64_t)g_k * ld + c]);
-  }
-}
-
-__device__ __forceinline__ void rw_finish(int cols, int col0, int k0,
-                                          int kz1, int s_row,
-                                          bf16x8 (&v)[2]) {
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-    if (!(k0 + s_row + 32 * h < kz1 && col0 + 8 <= cols)) v[h] = bf16x8{};
-}
-
 __global__ __launch_bounds__(512)
 void relation_wgrad_kernel(const RwPack P) {
-  alignas(16) __shared__ unsigned char As[RBK * W_ROW_BYTES];   // [k][m]
-  alignas(16) __shared__ unsigned char Bs[RBK * W_ROW_BYTES];   // [k][n]
-  __shared__ float dbs[WBT][4];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave >> 2;                // 64 rows each
-  const int wn = wave & 3;                 // 32 cols each
+  alignas(16) __shared__ unsigned char As[KM_TILE_BYTES];   // [k][m]
+  alignas(16) __shared__ unsigned char Bs[KM_TILE_BYTES];   // [k][n]
+  __shared__ float dbs[KM_BT][4];
 
   const int wg = (int)blockIdx.x;
   int si = 0;
@@ -478,92 +275,21 @@ void relation_wgrad_kernel(const RwPack P) {
   const int chunk = local / S.m_t;
   const int M = S.M, N = S.N;
   const int a_cols = (M + 7) & ~7;         // readable columns of A
-  const int block_row = mt * WBT, block_col = nt * WBT;
+  const int block_row = mt * KM_BT, block_col = nt * KM_BT;
   const int kz0 = chunk * P.k_per_z;
   const int kz1 = min(kz0 + P.k_per_z, S.Kb);
-  const __bf16* __restrict__ A = S.A;
-  const __bf16* __restrict__ B = S.B;
-
-  f32x4g acc[4][2] = {};
-
-  const int s_row = tid >> 4;              // 0..31 (+32)
-  const int s_ch = tid & 15;
-  const int fg8 = (lane >> 4) * 8;
-
-  // db: thread (m_l, phase) sums rows phase, phase + 4, ... of column m_l
-  const int m_l = tid & 127, phase = tid >> 7;
   const bool do_db = S.with_db != 0 && nt == 0;
+
+  // both widths are multiples of 8: no chunk straddles an edge
+  f32x4 acc[4][2] = {};
   float dsum = 0.f;
-
-  const int a_col = block_row + s_ch * 8, b_col = block_col + s_ch * 8;
-  bf16x8 va[2], vb[2];
-  rw_issue(A, S.lda, a_cols, a_col, kz0, kz1, s_row, va);
-  rw_issue(B, S.ldb, N, b_col, kz0, kz1, s_row, vb);
-
-  for (int k0 = kz0; k0 < kz1; k0 += RBK) {
-    rw_finish(a_cols, a_col, k0, kz1, s_row, va);
-    rw_finish(N, b_col, k0, kz1, s_row, vb);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      *reinterpret_cast<bf16x8*>(
-          As + rw_tile_off(s_row + 32 * h, s_ch)) = va[h];
-      *reinterpret_cast<bf16x8*>(
-          Bs + rw_tile_off(s_row + 32 * h, s_ch)) = vb[h];
-    }
-    __syncthreads();
-    if (k0 + RBK < kz1) {
-      rw_issue(A, S.lda, a_cols, a_col, k0 + RBK, kz1, s_row, va);
-      rw_issue(B, S.ldb, N, b_col, k0 + RBK, kz1, s_row, vb);
-    }
-#pragma unroll
-    for (int kk = 0; kk < RBK; kk += 32) {
-      bf16x8 a[4], b[2];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        a[i] = rw_frag(As, kk + fg8, wm * 8 + i * 2, lane);
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        b[j] = rw_frag(Bs, kk + fg8, wn * 4 + j * 2, lane);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-    if (do_db) {
-      // ascending k; the zero rows past kz1 add +0
-#pragma unroll
-      for (int r = 0; r < RBK; r += 4)
-        dsum += (float)*reinterpret_cast<const __bf16*>(
-            As + rw_tile_off(r + phase, m_l >> 3) + 2 * (m_l & 7));
-    }
-    __syncthreads();
-  }
-
-  const int c_col = lane & 15;
-  const int c_row0 = (lane >> 4) * 4;
+  km_k_loop(As, Bs, S.A, S.lda, a_cols, false, S.B, S.ldb, N, false,
+            block_row, block_col, kz0, kz1, do_db, acc, dsum);
   float* const Cz = S.P + (int64_t)chunk * S.plane;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = block_row + wm * 64 + i * 16 + c_row0 + r;
-        const int col = block_col + wn * 32 + j * 16 + c_col;
-        if (row < M && col < N) Cz[(int64_t)row * N + col] = acc[i][j][r];
-      }
-    }
-  }
-  if (do_db) {
-    dbs[m_l][phase] = dsum;
-    __syncthreads();
-    if (tid < WBT && block_row + tid < M)
-      Cz[(int64_t)M * N + block_row + tid] =
-          dbs[tid][0] + dbs[tid][1] + dbs[tid][2] + dbs[tid][3];
-  }
+  km_store_plane(Cz, Cz + (int64_t)M * N, dbs, M, N, block_row, block_col,
+                 acc, do_db, dsum);
 }
+
 
 // out[e] = sum over chunks c, ascending, of P[c * plane + e]: dW and db of
 // one segment per blockIdx.y, zeros for a segment without chunks.
@@ -896,12 +622,12 @@ hip_relation_linear_wgrad(const std::vector<torch::Tensor>& dym,
     R.Kb = (int)Kb;
     R.M = (int)M;
     R.N = (int)N;
-    R.m_t = (int)((M + WBT - 1) / WBT);
-    R.n_t = (int)((N + WBT - 1) / WBT);
+    R.m_t = (int)((M + KM_BT - 1) / KM_BT);
+    R.n_t = (int)((N + KM_BT - 1) / KM_BT);
     R.with_db = with_db[s] ? 1 : 0;
-    steps += (int64_t)R.m_t * R.n_t * ((Kb + RBK - 1) / RBK);
+    steps += (int64_t)R.m_t * R.n_t * ((Kb + MT_BK - 1) / MT_BK);
   }
-  const int64_t k_per_z = std::max<int64_t>(1, (steps + 1023) / 1024) * RBK;
+  const int64_t k_per_z = std::max<int64_t>(1, (steps + 1023) / 1024) * MT_BK;
   int64_t planes = 0, outs = 0, items = 0, most = 0;
   std::vector<int64_t> z(S), p_off(S), o_off(S);
   for (size_t s = 0; s < S; ++s) {

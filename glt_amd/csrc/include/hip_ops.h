@@ -273,7 +273,9 @@ struct GemmBtPlan {
 };
 GemmBtPlan gemm_bt_bf16_plan(int64_t M, int64_t K, int64_t N,
                              bool aligned = true);
-// Byte offset of a 16-byte chunk in the wide kernel's LDS tile images.
+// Byte offset of a 16-byte chunk in the staged [rows][64] LDS images that
+// gemm_bt_wide_kernel and relation_gemm_kernel store and read through
+// (rm_tile_off of hip_mfma_tile.h).
 int64_t gemm_bt_tile_offset(int64_t row, int64_t chunk);
 // (dW, db) = (A[Kb,M]^T @ B[Kb,N], colsum A), fp32 outputs (split-K).
 std::tuple<torch::Tensor, c10::optional<torch::Tensor>> hip_gemm_kt_bf16(
@@ -285,7 +287,9 @@ struct GemmKtPlan {
   int64_t m_t, n_t, z, k_per_z;
 };
 GemmKtPlan gemm_kt_bf16_plan(int64_t Kb, int64_t M, int64_t N);
-// Byte offset of a 16-byte chunk in the 128x128 kernel's LDS tile image.
+// Byte offset of a 16-byte chunk in the [64][128] LDS tile image that
+// gemm_kt128_kernel and relation_wgrad_kernel store and read through
+// (km_tile_off of hip_mfma_tile.h).
 int64_t gemm_kt_tile_offset(int64_t row, int64_t chunk);
 torch::Tensor hip_mfma_bf16_selftest(const torch::Tensor& A,
                                      const torch::Tensor& B);

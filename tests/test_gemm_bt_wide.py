@@ -4,11 +4,14 @@ of the two.
 
 A. Plan and layout, without a GPU.  `_C.gemm_bt_bf16_plan(M, K, N)` is the
    launcher's own dispatch.  `_C.gemm_bt_tile_offset(row, chunk)` is the one
-   function the kernel stores and reads its staged tiles through: the byte
-   offset of 16-byte chunk `chunk` (k = 8*chunk .. 8*chunk+7) of row `row`
-   of a [rows][64] bf16 image (64 rows of A, 256 of Bt).  The tests form
-   the addresses the kernel's lanes form and check them against the LDS
-   rules of the hardware: a 16-byte store is banked by (addr / 4) % 32 over
+   function gemm_bt_wide_kernel and relation_gemm_kernel store and read
+   their staged tiles through: the byte offset of 16-byte chunk `chunk`
+   (k = 8*chunk .. 8*chunk+7) of row `row` of a [rows][64] bf16 image (64
+   rows of A and 256 of Bt in the wide kernel; 64 of A and 128 of W, a
+   prefix of the same rule with the same lane maps, in the grouped one).
+   The tests form the addresses the kernels' lanes form and check them
+   against the LDS rules of the hardware: a 16-byte store is banked by
+   (addr / 4) % 32 over
    each group of 8 consecutive lanes; a 16-byte read by (addr / 4) % 64
    over four groups of 16 lanes, {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}
    and the same two shifted by 32.

@@ -2,9 +2,10 @@
 the register prefetch of the next K step and db from the staged tile.
 
 A. Layout, without a GPU.  `_C.gemm_kt_tile_offset(row, chunk)` is the one
-   function the kernel stores and reads through: the byte offset of 16-byte
-   chunk `chunk` (columns 8*chunk .. 8*chunk+7) of k row `row` in a
-   [64][128] bf16 tile.  The tests rebuild from it where every element
+   function gemm_kt128_kernel and relation_wgrad_kernel (same tile, same
+   lane maps) store and read through: the byte offset of 16-byte chunk
+   `chunk` (columns 8*chunk .. 8*chunk+7) of k row `row` in a [64][128]
+   bf16 tile.  The tests rebuild from it where every element
    lies, then form the addresses the kernel's lanes form and check them
    against the LDS rules of the hardware: a transposed 8-byte read needs an
    8-byte-aligned address of 4 contiguous elements of one row and is banked

@@ -19,6 +19,7 @@ RGNN / HeteroConv switch that reaches it.
 import pytest
 import torch
 
+from glt_amd import _C
 from glt_amd.ops import relation_linear, relation_linear_uses_kernel
 
 BF16 = torch.bfloat16
@@ -170,6 +171,34 @@ def test_relation_linear_bound(relu):
             _assert_bounded(bd[s].grad, ref["db"][s],
                             _gamma(m + 5) * ref["dbmag"][s], False,
                             "db[%d]" % s)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["wide", "narrow"])
+@pytest.mark.parametrize("shape", [(65, 72, 136), (130, 200, 257)],
+                         ids=lambda s: "x".join(map(str, s)))
+def test_relation_linear_one_segment_is_gemm_bt(shape, which, monkeypatch):
+    """One group of one segment is the dense projection: relation_gemm_kernel
+    and gemm_bt_wide_kernel run one K loop and one epilogue, and
+    test_gemm_bt_wide.py pins the 64x64 kernel to the wide one, so all
+    three agree bit for bit on real-valued input.  The shapes give a partial
+    row tile and a K tail inside a 64-step; N = 136 a dead wave and 16-byte
+    rows, N = 257 element stores and a one-column tile."""
+    M, K, N = shape
+    monkeypatch.delenv("GLT_GEMM_PERSIST", raising=False)
+    monkeypatch.setenv("GLT_GEMM_BT", which)
+    assert _C.gemm_bt_bf16_plan(M, K, N)[0] == which
+    g = torch.Generator().manual_seed(70 + M)
+    x = torch.randn(M, K, generator=g).to(BF16).cuda()
+    w = torch.randn(N, K, generator=g).to(BF16).cuda()
+    b = torch.randn(N, generator=g).cuda()
+    assert relation_linear_uses_kernel([x], [w], [0], [M])
+    for bias in (b, None):
+        for relu in (False, True):
+            y, = relation_linear([x], [w], [bias], [0], [M], relu=relu)
+            want = _C.gemm_bt_bf16(x, w, bias, relu, False)
+            assert y.dtype == want.dtype == BF16
+            assert torch.equal(y, want), (bias is not None, relu)
 
 
 def test_relation_linear_composition_and_validation():
