@@ -341,6 +341,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out"), py::arg("m"), py::arg("z"), py::arg("dout"),
         py::arg("slope"), py::arg("src_off") = py::none(),
         py::arg("in_edge") = py::none());
+  m.def("tconv_fwd", &hip_tconv_fwd, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("ee"), py::arg("src"), py::arg("offsets"), py::arg("n_tgt"),
+        py::arg("scale"), py::arg("for_backward") = false);
+  m.def("tconv_bwd", &hip_tconv_bwd, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("ee"), py::arg("tgt"), py::arg("src"), py::arg("offsets"),
+        py::arg("out"), py::arg("m"), py::arg("z"), py::arg("dout"),
+        py::arg("scale"), py::arg("need_dq") = true,
+        py::arg("need_dee") = false, py::arg("src_off") = py::none(),
+        py::arg("in_edge") = py::none());
   m.def("segment_mean_fwd", &hip_segment_mean_fwd);
   m.def("segment_mean_bwd", &hip_segment_mean_bwd, py::arg("dy"),
         py::arg("col"), py::arg("offsets"), py::arg("n_src"),

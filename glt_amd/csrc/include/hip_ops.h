@@ -253,6 +253,34 @@ hip_gatv2_bwd(const torch::Tensor& h_tgt, const torch::Tensor& h_src,
               double slope, const c10::optional<torch::Tensor>& src_off,
               const c10::optional<torch::Tensor>& in_edge);
 
+// --- fused dot-product attention with edge features (hip_tconv.hip) ---------
+// score_e[h] = scale * <q[t,h], k[src_e,h] + ee[e,h]>, softmax per target
+// segment, out[t] = sum_e p_e * (v[src_e] + ee[e]).  q [>= n_tgt, H, C],
+// k, v [n_src, H, C] may be row-strided views with a dense inner [H, C]
+// (column slices of one projection); ee is None or contiguous [E, H, C];
+// fp32 or bf16, 1 <= C <= 128; all arguments are validated before any
+// launch.  fwd returns (out, m, Z, out_f32) as hip_gatv2_fwd does.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor,
+           c10::optional<torch::Tensor>>
+hip_tconv_fwd(const torch::Tensor& q, const torch::Tensor& k,
+              const torch::Tensor& v, const c10::optional<torch::Tensor>& ee,
+              const torch::Tensor& src, const torch::Tensor& offsets,
+              int64_t n_tgt, double scale, bool for_backward);
+// Atomic-free backward: (dq, dk, dv, dee) in the inputs' dtype, contiguous,
+// every row written; each is None unless asked for: dq by need_dq, dee by
+// need_dee, dk and dv (by source) by giving (src_off, in_edge) =
+// hip_segment_transpose(src, n_src, nullopt).  out is the forward's out_f32.
+std::tuple<c10::optional<torch::Tensor>, c10::optional<torch::Tensor>,
+           c10::optional<torch::Tensor>, c10::optional<torch::Tensor>>
+hip_tconv_bwd(const torch::Tensor& q, const torch::Tensor& k,
+              const torch::Tensor& v, const c10::optional<torch::Tensor>& ee,
+              const torch::Tensor& tgt, const torch::Tensor& src,
+              const torch::Tensor& offsets, const torch::Tensor& out,
+              const torch::Tensor& m, const torch::Tensor& z,
+              const torch::Tensor& dout, double scale, bool need_dq,
+              bool need_dee, const c10::optional<torch::Tensor>& src_off,
+              const c10::optional<torch::Tensor>& in_edge);
+
 // --- f32 MFMA projection GEMM (hip_gemm_f32.hip) ----------------------------
 torch::Tensor hip_sage_gemm(const torch::Tensor& A, const torch::Tensor& B,
                             const c10::optional<torch::Tensor>& bias,

@@ -9,7 +9,7 @@ source/neighbor local index; aggregation flows 1 -> 0.
 Dense math lands on hipBLASLt through torch.nn.Linear (or the in-house
 MFMA GEMM for skinny shapes); sparse aggregation uses the fused HIP
 kernels in csrc/hip/ (segment-mean [+root concat], weighted segment sum,
-GAT / GATv2 edge-softmax) on GPU fp32/bf16 batches, with an index_add_ fallback
+GAT / GATv2 / TransformerConv edge-softmax) on GPU fp32/bf16 batches, with an index_add_ fallback
 for CPU/other dtypes.
 """
 
@@ -463,4 +463,108 @@ class GATv2Conv(nn.Module):
             if self.concat else out.mean(dim=1)
         if self.bias is not None:
             out = out + self.bias.to(out.dtype)
+        return out
+
+
+class TransformerConv(nn.Module):
+    """Multi-head dot-product graph attention with edge features (Shi et
+    al., "Masked Label Prediction", the UniMP layer; PyG's TransformerConv).
+
+    Per head, the score of an edge is ``<lin_query(x_tgt), lin_key(x_src) +
+    lin_edge(edge_attr)> / sqrt(C)``, a softmax over each target's edges
+    weighs the messages ``lin_value(x_src) + lin_edge(edge_attr)``; with
+    ``root_weight`` the target's ``lin_skip(x_tgt)`` is added, through a
+    learned gate when ``beta`` is set.  Parameter names follow PyG
+    (``lin_key``, ``lin_query``, ``lin_value``, ``lin_edge`` without bias,
+    ``lin_skip``, ``lin_beta``), so state dicts port.
+
+    GPU fp32 / bf16 batches sorted by target with C <= 128 run the fused
+    HIP kernels (ops.transformer_attention), whose backward has no float
+    atomics; everything else, and training with dropout > 0, runs the
+    torch composition.  Set ``use_fused = False`` to force the latter.
+    The skip connection and the gate are plain torch.
+    """
+
+    def __init__(self, in_channels, out_channels: int, heads: int = 1,
+                 concat: bool = True, beta: bool = False,
+                 dropout: float = 0.0, edge_dim: int = None,
+                 bias: bool = True, root_weight: bool = True):
+        super().__init__()
+        if isinstance(in_channels, int):
+            in_channels = (in_channels, in_channels)
+        in_src, in_tgt = in_channels
+        self.heads = heads
+        self.out_channels = out_channels
+        self.concat = concat
+        self.beta = beta and root_weight
+        self.dropout = dropout
+        self.edge_dim = edge_dim
+        self.root_weight = root_weight
+        self.use_fused = True
+        hc = heads * out_channels
+        self.lin_key = nn.Linear(in_src, hc, bias=bias)
+        self.lin_query = nn.Linear(in_tgt, hc, bias=bias)
+        self.lin_value = nn.Linear(in_src, hc, bias=bias)
+        self.lin_edge = nn.Linear(edge_dim, hc, bias=False) \
+            if edge_dim is not None else None
+        width = hc if concat else out_channels
+        self.lin_skip = nn.Linear(in_tgt, width, bias=bias) \
+            if root_weight else None
+        self.lin_beta = nn.Linear(3 * width, 1, bias=False) \
+            if self.beta else None
+
+    @staticmethod
+    def _project(lin, v):
+        if v.dtype != lin.weight.dtype:
+            from ..ops import cast_linear
+
+            return cast_linear(v, lin.weight, lin.bias)
+        return lin(v)
+
+    def forward(self, x, edge_index, edge_attr=None, num_target: int = None,
+                sorted_by_target: bool = True):
+        """x: [n, F] with the targets as its first ``num_target`` rows, or
+        a (x_target, x_source) tuple for bipartite edge sets;
+        edge_index[0] indexes the target side, edge_index[1] the source
+        side; edge_attr[i] ([E, edge_dim]) belongs to edge_index[:, i].
+        ``lin_query`` and ``lin_skip`` only run over the target rows.
+        sorted_by_target: set False for edge sets not sorted by
+        edge_index[0]; they take the composition."""
+        from ..ops import (transformer_attention,
+                           transformer_attention_composition)
+
+        x_tgt, x_src = x if isinstance(x, tuple) else (x, x)
+        nt = num_target if num_target is not None else x_tgt.size(0)
+        x_tgt = x_tgt[:nt]
+        H, C = self.heads, self.out_channels
+        q = self._project(self.lin_query, x_tgt).view(nt, H, C)
+        k = self._project(self.lin_key, x_src).view(-1, H, C)
+        v = self._project(self.lin_value, x_src).view(-1, H, C)
+        edge = None
+        if self.lin_edge is not None:
+            if edge_attr is None:
+                raise ValueError("TransformerConv: edge_dim is set, "
+                                 "edge_attr is required")
+            edge = self._project(self.lin_edge, edge_attr).view(-1, H, C)
+        elif edge_attr is not None:
+            raise ValueError("TransformerConv: edge_attr given to a layer "
+                             "built without edge_dim")
+        tgt, src = edge_index[0], edge_index[1]
+        if self.training and self.dropout > 0:
+            # no fused attention dropout
+            out = transformer_attention_composition(
+                q, k, v, tgt, src, nt, edge, dropout=self.dropout)
+        else:
+            out = transformer_attention(
+                q, k, v, tgt, src, nt, edge,
+                sorted_by_target=sorted_by_target and self.use_fused)
+        out = out.reshape(nt, H * C) if self.concat else out.mean(dim=1)
+        if self.lin_skip is not None:
+            x_r = self._project(self.lin_skip, x_tgt).to(out.dtype)
+            if self.lin_beta is not None:
+                gate = torch.sigmoid(self._project(
+                    self.lin_beta, torch.cat([out, x_r, out - x_r], dim=-1)))
+                out = gate * x_r + (1 - gate) * out
+            else:
+                out = out + x_r
         return out

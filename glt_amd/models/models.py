@@ -1,12 +1,14 @@
 """Model families exercised by the reference examples: GraphSAGE
-(supervised + unsupervised link-pred), GAT, GCN."""
+(supervised + unsupervised link-pred), GAT, GCN, and GraphTransformer
+(UniMP-style TransformerConv stack over edge-featured batches)."""
 from typing import Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .layers import GATConv, GATv2Conv, GCNConv, SAGEConv
+from .layers import (GATConv, GATv2Conv, GCNConv, SAGEConv,
+                     TransformerConv)
 
 
 def _layer_trim(num_sampled_nodes, num_sampled_edges, num_layers, layer):
@@ -126,6 +128,52 @@ class GAT(nn.Module):
                 x = conv(x, edge_index)
             if i < L - 1:
                 x = F.elu(x)
+                x = F.dropout(x, p=self.dropout, training=self.training)
+        return x
+
+
+class GraphTransformer(nn.Module):
+    """A stack of TransformerConv layers: ``heads`` concatenated heads on
+    the hidden layers, one averaged head on the last.
+
+    Same forward contract and trim-list handling as GAT, plus the batch's
+    ``edge_attr`` (``NeighborLoader(..., with_edge=True)``) when built with
+    ``edge_dim``.  The layers rely on ``data.edge_attr[i]`` belonging to
+    ``edge_index[:, i]``: the samplers concatenate rows, cols and edge ids
+    hop by hop in one order and the loader gathers the edge features by
+    those ids, so a layer's edge prefix ``edge_index[:, :n_edges]`` goes
+    with ``edge_attr[:n_edges]``.
+    """
+
+    def __init__(self, in_channels: int, hidden_channels: int,
+                 out_channels: int, num_layers: int, heads: int = 4,
+                 dropout: float = 0.0, edge_dim: Optional[int] = None):
+        super().__init__()
+        self.convs = nn.ModuleList()
+        dim = in_channels
+        for _ in range(num_layers - 1):
+            self.convs.append(TransformerConv(dim, hidden_channels,
+                                              heads=heads,
+                                              edge_dim=edge_dim))
+            dim = hidden_channels * heads
+        self.convs.append(TransformerConv(dim, out_channels, heads=1,
+                                          concat=False, edge_dim=edge_dim))
+        self.dropout = dropout
+
+    def forward(self, x, edge_index, num_sampled_nodes=None,
+                num_sampled_edges=None, edge_attr=None):
+        L = len(self.convs)
+        for i, conv in enumerate(self.convs):
+            trim = _layer_trim(num_sampled_nodes, num_sampled_edges, L, i)
+            if trim is not None:
+                n_in, n_edges, n_out = trim
+                x = conv(x[:n_in], edge_index[:, :n_edges],
+                         None if edge_attr is None else edge_attr[:n_edges],
+                         num_target=n_out)
+            else:
+                x = conv(x, edge_index, edge_attr)
+            if i < L - 1:
+                x = F.relu(x)
                 x = F.dropout(x, p=self.dropout, training=self.training)
         return x
 

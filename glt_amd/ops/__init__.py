@@ -6,6 +6,9 @@ from .linear import cast_linear, mfma_linear, use_mfma_linear
 from .gat import (gat_softmax_aggregate, gatv2_composition,
                   gatv2_softmax_aggregate)
 from .relation import relation_linear, relation_linear_uses_kernel
+from .attention import (transformer_attention,
+                        transformer_attention_composition,
+                        transformer_attention_fused_ok)
 
 __all__ = ["segment_mean", "segment_mean_cat", "segment_weighted_sum",
            "segment_max", "segment_min", "segment_max_cat",
@@ -14,4 +17,6 @@ __all__ = ["segment_mean", "segment_mean_cat", "segment_weighted_sum",
            "is_deterministic", "cast_linear",
            "mfma_linear", "use_mfma_linear", "gat_softmax_aggregate",
            "gatv2_softmax_aggregate", "gatv2_composition",
-           "relation_linear", "relation_linear_uses_kernel"]
+           "relation_linear", "relation_linear_uses_kernel",
+           "transformer_attention", "transformer_attention_composition",
+           "transformer_attention_fused_ok"]

@@ -265,6 +265,70 @@ def gatv2_table(device, iters, warmup, rounds=5):
                 print(f"gatv2 {name} {label}: "
                       f"{spread([timed(fn) for _ in range(rounds)])}")
 
+def tconv_table(device, iters, warmup, rounds=5):
+    """--op tconv: dot-product attention (ops.transformer_attention) forward
+    + backward with every gradient at the gat_fused flagship shape, with
+    and without projected edge features, fused kernels against the torch
+    composition, fp32 and bf16.  The two are timed alternately, `rounds`
+    times `iters` calls each, from device events; median, range and every
+    round, ms per call."""
+    from glt_amd.ops import (transformer_attention,
+                             transformer_attention_composition)
+
+    def timed(fn):
+        a = torch.cuda.Event(enable_timing=True)
+        b = torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / iters
+
+    def spread(ts):
+        return "%.3f ms (%.3f - %.3f) [%s]" % (
+            sorted(ts)[len(ts) // 2], min(ts), max(ts),
+            " ".join("%.3f" % t for t in ts))
+
+    k32, _, tgt, src, n_tgt = build_flagship_shapes("gat_fused", device)
+    n_src, H, C = k32.shape
+    E = src.numel()
+    print(f"tconv shape: n_src {n_src}, n_tgt {n_tgt}, E {E}, H {H}, C {C}")
+    v32 = torch.randn(n_src, H, C, device=device)
+    q32 = torch.randn(n_tgt, H, C, device=device)
+    e32 = torch.randn(E, H, C, device=device)
+    g32 = torch.randn(n_tgt, H, C, device=device)
+    for dtype in (torch.float32, torch.bfloat16):
+        name = "bf16" if dtype == torch.bfloat16 else "fp32"
+        for with_ee in (False, True):
+            ins = [x.to(dtype).requires_grad_(True) for x in
+                   ((q32, k32, v32, e32) if with_ee else (q32, k32, v32))]
+            edge = ins[3] if with_ee else None
+            dout = g32.to(dtype)
+
+            def step(fn):
+                for x in ins:
+                    x.grad = None
+                fn(ins[0], ins[1], ins[2], tgt, src, n_tgt,
+                   edge=edge).backward(dout)
+
+            fused = lambda: step(transformer_attention)
+            comp = lambda: step(transformer_attention_composition)
+            for _ in range(warmup):
+                fused()
+                comp()
+            tf, tc = [], []
+            for _ in range(rounds):
+                tf.append(timed(fused))
+                tc.append(timed(comp))
+            print(f"tconv {name} {'with' if with_ee else 'no'} ee fwd+bwd: "
+                  f"fused {spread(tf)}, composition {spread(tc)}, ratio of "
+                  f"medians "
+                  f"{sorted(tc)[rounds // 2] / sorted(tf)[rounds // 2]:.2f}x,"
+                  f" every fused round faster: {max(tf) < min(tc)}")
+
+
 # One layer of `bench_hetero.py --model rsage --dtype bf16` (1M papers, batch
 # 512, fanout 10,5, 4 relations; layer 0: K = 128, N = 256): rows per node type and, per
 # segment, (type, rows).  Every relation's aggregate covers all rows of its
@@ -358,7 +422,8 @@ def main():
                              "seg_wsum", "seg_wsum_bf16", "gcn_conv",
                              "gcn_conv_composite", "seg_max", "seg_max_cat",
                              "sage_conv_max", "sage_conv_max_composite",
-                             "seg_bwd", "gatv2", "relation_linear"])
+                             "seg_bwd", "gatv2", "relation_linear",
+                             "tconv"])
     ap.add_argument("--bf16", action="store_true",
                     help="gcn_conv, seg_mean, seg_max and sage_conv_max "
                          "ops: bf16 input at F=100 (default fp32 at F=256)")
@@ -381,6 +446,9 @@ def main():
         return
     if args.op == "relation_linear":
         relation_linear_table(device, args.iters, args.warmup)
+        return
+    if args.op == "tconv":
+        tconv_table(device, args.iters, args.warmup)
         return
     inp = build_flagship_shapes(args.op, device, args.bf16)
 
