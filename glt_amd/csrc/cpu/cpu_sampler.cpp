@@ -138,7 +138,8 @@ cpu_sample_neighbors(const torch::Tensor& indptr, const torch::Tensor& indices,
           cdf[j] = acc;
         }
         for (int64_t j = 0; j < kk; ++j) {
-          double r = (double)rng.uniform_float() * acc;
+          // r in (0, acc]: r == 0 would select a leading zero-weight edge
+          double r = (1.0 - (double)rng.uniform_float()) * acc;
           int64_t idx = std::lower_bound(cdf.begin(), cdf.end(), r) -
                         cdf.begin();
           if (idx >= deg) idx = deg - 1;

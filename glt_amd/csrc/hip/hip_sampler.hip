@@ -80,8 +80,8 @@ __global__ void sample_gather_kernel(
 // ---------------------------------------------------------------------------
 // Small-row fast path (deg <= 64, with-replacement): the row's weights
 // live one-per-lane in registers; the CDF is a wave shfl-scan and each
-// draw is one ballot + ffs — no LDS, no barriers.  Rows with deg > 64
-// are left to the block kernel below (and vice versa).
+// draw is a 6-step binary search by lane shuffles — no LDS, no barriers.
+// Rows with deg > 64 are left to the block kernel below (and vice versa).
 template <bool WITH_EID>
 __global__ void weighted_sample_wave_kernel(
     const int64_t* __restrict__ indptr, const int64_t* __restrict__ indices,
@@ -119,14 +119,22 @@ __global__ void weighted_sample_wave_kernel(
       if (lane >= sft) c += p;
     }
     const float tot = __shfl(c, kWave - 1);
-    // all k draws in parallel: lane j serves draw j with a fixed
-    // 6-step binary search over the register CDF via lane shuffles
-    for (int64_t j = lane; j < k; j += kWave) {
+    // All k draws in parallel: lane j serves draw j with a fixed 6-step
+    // binary search over the register CDF via lane shuffles.  All 64 lanes
+    // are live at every shuffle: r, deg, k and tot are wave-uniform, so is
+    // every branch above, and this loop runs ceil(k / 64) rounds for the
+    // whole wave.  Lanes with j >= k search too (a lane in k..deg-1 holds a
+    // CDF entry that the others read); only their stores are masked.  A
+    // shuffle from a lane outside the execution mask is not defined, and
+    // on CDNA reads 0.
+    for (int64_t j0 = 0; j0 < k; j0 += kWave) {
+      const int64_t j = j0 + lane;
       DRng rng(call_seed ^ (uint64_t)r * 0xD6E8FEB86659FD93ull ^
                (uint64_t)j * 0xA24BAED4963EE407ull);
       int64_t idx;
       if (tot > 0.f) {
-        const float u = rng.uniform_float() * tot;
+        // u in (0, tot]: u == 0 would select a leading zero-weight edge
+        const float u = (1.0f - rng.uniform_float()) * tot;
         int lo = 0, hi = (int)deg - 1;
 #pragma unroll
         for (int step = 0; step < 6; ++step) {
@@ -139,8 +147,10 @@ __global__ void weighted_sample_wave_kernel(
       } else {
         idx = (int64_t)rng.uniform((uint64_t)deg);
       }
-      out_nbrs[off + j] = indices[base + idx];
-      if (WITH_EID) out_eids[off + j] = eids[base + idx];
+      if (j < k) {
+        out_nbrs[off + j] = indices[base + idx];
+        if (WITH_EID) out_eids[off + j] = eids[base + idx];
+      }
     }
   }
 }
@@ -227,7 +237,8 @@ void weighted_sample_block_kernel(
       for (int64_t j = tid; j < k; j += 256) {
         DRng rng(call_seed ^ (uint64_t)r * 0xD6E8FEB86659FD93ull ^
                  (uint64_t)j * 0xA24BAED4963EE407ull);
-        const float u = rng.uniform_float() * tot;
+        // u in (0, tot]: u == 0 would select a leading zero-weight edge
+        const float u = (1.0f - rng.uniform_float()) * tot;
         int lo = 0, hi = nch - 1;  // first chunk with cdf[c] >= u
         while (lo < hi) {
           const int mid = (lo + hi) >> 1;
