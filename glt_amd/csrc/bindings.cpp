@@ -277,8 +277,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def(py::init<std::vector<int64_t>, int64_t, int64_t, bool>(),
            py::arg("fanout"), py::arg("batch_cap"), py::arg("device") = 0,
            py::arg("with_eid") = false)
+      // no Python object is touched inside run(): the training thread can
+      // issue its own launches while the sampler thread issues the batch's
       .def("run", &DeferredSamplerPy::run, py::arg("indptr"),
-           py::arg("indices"), py::arg("edge_ids"), py::arg("seeds"));
+           py::arg("indices"), py::arg("edge_ids"), py::arg("seeds"),
+           py::call_guard<py::gil_scoped_release>());
 
   py::class_<FeatureStorePy>(m, "UnifiedFeatureStore")
       .def(py::init<int64_t>(), py::arg("device"))
@@ -358,6 +361,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("segment_mean_cat_bwd", &hip_segment_mean_cat_bwd, py::arg("dy"),
         py::arg("col"), py::arg("offsets"), py::arg("n_src"),
         py::arg("order_independent") = false);
+  m.def("segment_offsets", &hip_segment_offsets, py::arg("tgt"),
+        py::arg("n_tgt"));
   m.def("segment_transpose", &hip_segment_transpose, py::arg("col"),
         py::arg("n_src"), py::arg("tgt") = py::none());
   m.def("segment_mean_bwd_gather", &hip_segment_mean_bwd_gather,

@@ -19,16 +19,53 @@ namespace glt {
 namespace {
 
 constexpr uint64_t kEmpty = ~0ull;
+constexpr unsigned long long kNoIndex = 0x7FFFFFFFFFFFFFFFull;
+
+// One table slot: everything a probe needs lies in one 32-byte sector, so a
+// probe touches one cache line and the CAS on the key and the atomicMin on
+// the first index of one insert go to the same line.
+struct alignas(32) DSlot {
+  unsigned long long key;        // kEmpty until claimed
+  unsigned long long first_idx;  // least element index that inserted the key
+  int64_t local_id;              // -1 until d_assign_kernel numbers the key
+  int64_t pad;
+};
+static_assert(sizeof(DSlot) == 32, "one slot is one 32-byte sector");
 
 struct DTableView {
-  uint64_t* keys;
-  unsigned long long* first_idx;
-  int64_t* local_id;
+  DSlot* slots;
   uint64_t mask;
 };
 
 __device__ __forceinline__ uint64_t d_probe(uint64_t key, uint64_t mask) {
   return d_splitmix64(key) & mask;
+}
+
+// Sum of the first m entries of stats (m <= L + 1): the number of nodes
+// numbered before a hop.  Every kernel that needs the running count adds the
+// few entries itself; there is no separate counter to bump.
+__device__ __forceinline__ int64_t d_nodes_before(
+    const int64_t* __restrict__ stats, int m) {
+  int64_t s = 0;
+  for (int i = 0; i < m; ++i) s += stats[i];
+  return s;
+}
+
+// The whole per-batch reset in one launch: empties every slot and stores the
+// seed count the seed pass guards on.
+__global__ void d_reset_kernel(DTableView t, int64_t* __restrict__ seed_n,
+                               int64_t bs) {
+  const int64_t cap = (int64_t)t.mask + 1;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < cap;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    DSlot s;
+    s.key = kEmpty;
+    s.first_idx = kNoIndex;
+    s.local_id = -1;
+    s.pad = 0;
+    t.slots[i] = s;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) *seed_n = bs;
 }
 
 __global__ void d_fill_counts_kernel(const int64_t* __restrict__ indptr,
@@ -51,16 +88,24 @@ __global__ void d_fill_counts_kernel(const int64_t* __restrict__ indptr,
   }
 }
 
+// Samples hop `hop` and writes its rows as well: the frontier is the
+// previous hop's new nodes in rank order (the unique seeds for hop 0), so
+// frontier element r has local id (nodes numbered before the frontier) + r
+// and no table lookup is needed.  One thread also stores the hop's edge
+// total to stats_total.
 template <bool WITH_EID>
 __global__ void d_sample_gather_kernel(
     const int64_t* __restrict__ indptr, const int64_t* __restrict__ indices,
     const int64_t* __restrict__ eids, int64_t num_rows,
     const int64_t* __restrict__ seeds, const int64_t* __restrict__ n_dev,
     int64_t cap, int64_t k, const int64_t* __restrict__ offsets,
-    uint64_t call_seed, int64_t* __restrict__ out_nbrs,
-    int64_t* __restrict__ out_eids) {
+    uint64_t call_seed, const int64_t* __restrict__ stats, int hop,
+    int64_t* __restrict__ stats_total, int64_t* __restrict__ out_nbrs,
+    int64_t* __restrict__ out_eids, int64_t* __restrict__ out_rows) {
   const int64_t n = *n_dev;
   const int64_t total = offsets[n];
+  const int64_t frontier_base = d_nodes_before(stats, hop);
+  if (blockIdx.x == 0 && threadIdx.x == 0) *stats_total = total;
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
        e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = row_of(offsets, n, e);
@@ -77,33 +122,39 @@ __global__ void d_sample_gather_kernel(
     }
     out_nbrs[e] = indices[base + pos];
     if (WITH_EID) out_eids[e] = eids[base + pos];
+    out_rows[e] = frontier_base + r;
   }
 }
 
+// The one probe per element: claims or finds the key's slot, lowers the
+// slot's first index to i and records the slot for the flag, assign and
+// relabel passes, which then neither hash nor walk.
 __global__ void d_insert_kernel(DTableView t,
                                 const int64_t* __restrict__ ids,
                                 const int64_t* __restrict__ n_dev,
-                                int64_t cap) {
+                                int64_t cap, int32_t* __restrict__ slot_of) {
   const int64_t n = *n_dev;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < cap;
        i += (int64_t)gridDim.x * blockDim.x) {
     if (i >= n) continue;
-    uint64_t key = (uint64_t)ids[i];
+    const uint64_t key = (uint64_t)ids[i];
     uint64_t slot = d_probe(key, t.mask);
     for (;;) {
-      uint64_t prev = atomicCAS((unsigned long long*)&t.keys[slot],
-                                (unsigned long long)kEmpty,
-                                (unsigned long long)key);
+      const uint64_t prev =
+          atomicCAS(&t.slots[slot].key, (unsigned long long)kEmpty,
+                    (unsigned long long)key);
       if (prev == kEmpty || prev == key) {
-        atomicMin(&t.first_idx[slot], (unsigned long long)i);
+        atomicMin(&t.slots[slot].first_idx, (unsigned long long)i);
         break;
       }
       slot = (slot + 1) & t.mask;
     }
+    slot_of[i] = (int32_t)slot;
   }
 }
 
-__global__ void d_flag_kernel(DTableView t, const int64_t* __restrict__ ids,
+__global__ void d_flag_kernel(DTableView t,
+                              const int32_t* __restrict__ slot_of,
                               const int64_t* __restrict__ n_dev,
                               int64_t cap, int64_t* __restrict__ flags) {
   const int64_t n = *n_dev;
@@ -111,34 +162,33 @@ __global__ void d_flag_kernel(DTableView t, const int64_t* __restrict__ ids,
        i += (int64_t)gridDim.x * blockDim.x) {
     int64_t f = 0;
     if (i < n) {
-      const uint64_t key = (uint64_t)ids[i];
-      uint64_t slot = d_probe(key, t.mask);
-      while (t.keys[slot] != key) slot = (slot + 1) & t.mask;
-      f = (t.local_id[slot] < 0 && t.first_idx[slot] == (uint64_t)i) ? 1
-                                                                     : 0;
+      const DSlot& s = t.slots[slot_of[i]];
+      f = (s.local_id < 0 && s.first_idx == (unsigned long long)i) ? 1 : 0;
     }
     flags[i] = f;
   }
 }
 
+// Numbers the flagged (first-occurrence, not yet numbered) elements from
+// the sum of the first n_before entries of stats and stores the count of
+// new nodes to n_new_out, an entry of stats past those.
 __global__ void d_assign_kernel(DTableView t,
                                 const int64_t* __restrict__ ids,
+                                const int32_t* __restrict__ slot_of,
                                 const int64_t* __restrict__ n_dev,
                                 int64_t cap,
                                 const int64_t* __restrict__ ranks,
                                 const int64_t* __restrict__ flags,
-                                const int64_t* __restrict__ base_dev,
+                                const int64_t* __restrict__ stats,
+                                int n_before,
                                 int64_t* __restrict__ unique_out,
                                 int64_t* __restrict__ n_new_out) {
   const int64_t n = *n_dev;
-  const int64_t base = *base_dev;
+  const int64_t base = d_nodes_before(stats, n_before);
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < cap;
        i += (int64_t)gridDim.x * blockDim.x) {
     if (i < n && flags[i]) {
-      const uint64_t key = (uint64_t)ids[i];
-      uint64_t slot = d_probe(key, t.mask);
-      while (t.keys[slot] != key) slot = (slot + 1) & t.mask;
-      t.local_id[slot] = base + ranks[i] - 1;
+      t.slots[slot_of[i]].local_id = base + ranks[i] - 1;
       unique_out[ranks[i] - 1] = ids[i];
     }
   }
@@ -147,51 +197,21 @@ __global__ void d_assign_kernel(DTableView t,
   }
 }
 
-__global__ void d_bump_count_kernel(int64_t* __restrict__ count_dev,
-                                    const int64_t* __restrict__ n_new) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *count_dev += *n_new;
-}
-
+// out[i] = local id of the key element i inserted.  Every element below the
+// device count went through d_insert_kernel and its key was numbered by
+// this or an earlier d_assign_kernel, so each gets a local id >= 0.  The
+// one exception the contract leaves is the id -1: it equals the empty mark,
+// claims no slot of its own, and reads back whatever its recorded slot
+// holds, -1 where that slot was never numbered.
 __global__ void d_relabel_kernel(DTableView t,
-                                 const int64_t* __restrict__ ids,
+                                 const int32_t* __restrict__ slot_of,
                                  const int64_t* __restrict__ total_dev,
                                  int64_t cap, int64_t* __restrict__ out) {
   const int64_t n = *total_dev;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < cap;
        i += (int64_t)gridDim.x * blockDim.x) {
     if (i >= n) continue;
-    const uint64_t key = (uint64_t)ids[i];
-    uint64_t slot = d_probe(key, t.mask);
-    for (;;) {
-      const uint64_t kk = t.keys[slot];
-      if (kk == key) {
-        out[i] = t.local_id[slot];
-        break;
-      }
-      if (kk == kEmpty) {
-        out[i] = -1;
-        break;
-      }
-      slot = (slot + 1) & t.mask;
-    }
-  }
-}
-
-__global__ void d_expand_rows_kernel(DTableView t,
-                                     const int64_t* __restrict__ srcs,
-                                     const int64_t* __restrict__ ns_dev,
-                                     int64_t cap_rows,
-                                     const int64_t* __restrict__ offsets,
-                                     int64_t* __restrict__ rows) {
-  const int64_t ns = *ns_dev;
-  const int64_t total = offsets[ns];
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-       e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = row_of(offsets, ns, e);
-    const uint64_t key = (uint64_t)srcs[r];
-    uint64_t slot = d_probe(key, t.mask);
-    while (t.keys[slot] != key) slot = (slot + 1) & t.mask;
-    rows[e] = t.local_id[slot];
+    out[i] = t.slots[slot_of[i]].local_id;
   }
 }
 
@@ -227,9 +247,10 @@ class DeferredSampler {
     for (auto c : node_cap_) total_node_cap_ += c;
     // hash table sized for every node of the batch
     table_cap_ = d_next_pow2(total_node_cap_ * 2);
-    keys_ = torch::empty({table_cap_}, opts);
-    first_idx_ = torch::empty({table_cap_}, opts);
-    local_id_ = torch::empty({table_cap_}, opts);
+    TORCH_CHECK(table_cap_ <= ((int64_t)1 << 31),
+                "deferred: table too large for 32-bit slot records");
+    table_ = torch::empty({table_cap_ * (int64_t)(sizeof(DSlot) / 8)}, opts);
+    auto slot_opts = opts.dtype(torch::kInt32);
     for (size_t h = 0; h < fanout_.size(); ++h) {
       const int64_t rc = node_cap_[h];
       const int64_t ec = node_cap_[h + 1];
@@ -242,10 +263,11 @@ class DeferredSampler {
       cols_.push_back(torch::empty({ec}, opts));
       uniq_.push_back(torch::empty({ec}, opts));
       flags_.push_back(torch::empty({ec}, opts));
+      slot_.push_back(torch::empty({ec}, slot_opts));
     }
-    count_dev_ = torch::zeros({1}, opts);
     seed_uniq_ = torch::empty({batch_cap}, opts);
     seed_flags_ = torch::empty({batch_cap}, opts);
+    seed_slot_ = torch::empty({batch_cap}, slot_opts);
     seed_n_ = torch::zeros({1}, opts);
     stats_ = torch::zeros({(int64_t)(2 * fanout_.size() + 1)}, opts);
   }
@@ -271,112 +293,82 @@ class DeferredSampler {
     const int64_t num_rows = indptr.size(0) - 1;
     const int64_t bs = seeds.size(0);
     TORCH_CHECK(bs <= node_cap_[0], "batch exceeds deferred capacity");
-    // reset table + running count
-    keys_.fill_(-1);
-    first_idx_.fill_(0x7FFFFFFFFFFFFFFFll);
-    local_id_.fill_(-1);
-    count_dev_.zero_();
-    seed_n_.fill_(bs);
-
     DTableView t = view();
+    int64_t* stats = stats_.data_ptr<int64_t>();
+    // empty table + seed count, one launch
+    hipLaunchKernelGGL(d_reset_kernel, dim3(grid_for(table_cap_)),
+                       dim3(kBlock), 0, stream, t,
+                       seed_n_.data_ptr<int64_t>(), bs);
     // dedup seeds
     hipLaunchKernelGGL(d_insert_kernel, dim3(grid_for(bs)), dim3(kBlock), 0,
                        stream, t, seeds.data_ptr<int64_t>(),
-                       seed_n_.data_ptr<int64_t>(), bs);
+                       seed_n_.data_ptr<int64_t>(), bs,
+                       seed_slot_.data_ptr<int32_t>());
     hipLaunchKernelGGL(d_flag_kernel, dim3(grid_for(bs)), dim3(kBlock), 0,
-                       stream, t, seeds.data_ptr<int64_t>(),
+                       stream, t, seed_slot_.data_ptr<int32_t>(),
                        seed_n_.data_ptr<int64_t>(), bs,
                        seed_flags_.data_ptr<int64_t>());
     auto seed_ranks = torch::cumsum(seed_flags_.narrow(0, 0, bs), 0);
     hipLaunchKernelGGL(d_assign_kernel, dim3(grid_for(bs)), dim3(kBlock), 0,
                        stream, t, seeds.data_ptr<int64_t>(),
+                       seed_slot_.data_ptr<int32_t>(),
                        seed_n_.data_ptr<int64_t>(), bs,
                        seed_ranks.data_ptr<int64_t>(),
-                       seed_flags_.data_ptr<int64_t>(),
-                       count_dev_.data_ptr<int64_t>(),
+                       seed_flags_.data_ptr<int64_t>(), stats, 0,
                        seed_uniq_.data_ptr<int64_t>(),
-                       stats_.data_ptr<int64_t>());  // stats[0] = n_seed
-    hipLaunchKernelGGL(d_bump_count_kernel, dim3(1), dim3(64), 0, stream,
-                       count_dev_.data_ptr<int64_t>(),
-                       stats_.data_ptr<int64_t>());
+                       stats);  // stats[0] = n_seed
 
     const int64_t L = (int64_t)fanout_.size();
     const int64_t* eid_ptr =
         edge_ids.has_value() ? edge_ids->data_ptr<int64_t>() : nullptr;
     torch::Tensor frontier = seed_uniq_;
-    torch::Tensor frontier_n = stats_.narrow(0, 0, 1);
     for (int64_t h = 0; h < L; ++h) {
       const int64_t rc = node_cap_[h];
       const int64_t ec = node_cap_[h + 1];
       const int64_t k = fanout_[h];
+      const int64_t* frontier_n = stats + h;
       const uint64_t cs = SeedManager::instance().next_call_seed();
       hipLaunchKernelGGL(d_fill_counts_kernel, dim3(grid_for(rc)),
                          dim3(kBlock), 0, stream,
                          indptr.data_ptr<int64_t>(), num_rows,
-                         frontier.data_ptr<int64_t>(),
-                         frontier_n.data_ptr<int64_t>(), rc, k,
+                         frontier.data_ptr<int64_t>(), frontier_n, rc, k,
                          counts_[h].data_ptr<int64_t>());
       {
         auto v = offsets_[h].narrow(0, 1, rc);
         torch::cumsum_out(v, counts_[h], 0);
       }
-      if (with_eid_ && eid_ptr) {
-        hipLaunchKernelGGL((d_sample_gather_kernel<true>),
-                           dim3(grid_for(ec)), dim3(kBlock), 0, stream,
-                           indptr.data_ptr<int64_t>(),
-                           indices.data_ptr<int64_t>(), eid_ptr, num_rows,
-                           frontier.data_ptr<int64_t>(),
-                           frontier_n.data_ptr<int64_t>(), rc, k,
-                           offsets_[h].data_ptr<int64_t>(), cs,
-                           nbrs_[h].data_ptr<int64_t>(),
-                           eids_[h].data_ptr<int64_t>());
-      } else {
-        hipLaunchKernelGGL((d_sample_gather_kernel<false>),
-                           dim3(grid_for(ec)), dim3(kBlock), 0, stream,
-                           indptr.data_ptr<int64_t>(),
-                           indices.data_ptr<int64_t>(), eid_ptr, num_rows,
-                           frontier.data_ptr<int64_t>(),
-                           frontier_n.data_ptr<int64_t>(), rc, k,
-                           offsets_[h].data_ptr<int64_t>(), cs,
-                           nbrs_[h].data_ptr<int64_t>(), nullptr);
-      }
-      // total edges of this hop -> stats[L + 1 + h] (device-device, async)
-      stats_.narrow(0, 1 + L + h, 1).copy_(offsets_[h].narrow(0, rc, 1));
-      // rows of hop h (expand frontier local ids over segments)
-      hipLaunchKernelGGL(d_expand_rows_kernel, dim3(grid_for(ec)),
-                         dim3(kBlock), 0, stream, t,
-                         frontier.data_ptr<int64_t>(),
-                         frontier_n.data_ptr<int64_t>(), rc,
-                         offsets_[h].data_ptr<int64_t>(),
-                         rows_[h].data_ptr<int64_t>());
+      // neighbours, edge ids and rows of hop h; the hop's edge total goes
+      // to stats[L + 1 + h] from the same launch
+      const bool eid = with_eid_ && eid_ptr;
+      hipLaunchKernelGGL(
+          eid ? d_sample_gather_kernel<true> : d_sample_gather_kernel<false>,
+          dim3(grid_for(ec)), dim3(kBlock), 0, stream,
+          indptr.data_ptr<int64_t>(), indices.data_ptr<int64_t>(), eid_ptr,
+          num_rows, frontier.data_ptr<int64_t>(), frontier_n, rc, k,
+          offsets_[h].data_ptr<int64_t>(), cs, stats, (int)h,
+          stats + L + 1 + h, nbrs_[h].data_ptr<int64_t>(),
+          eid ? eids_[h].data_ptr<int64_t>() : nullptr,
+          rows_[h].data_ptr<int64_t>());
       // insert neighbors, assign fresh local ids
-      auto total_dev = offsets_[h].narrow(0, rc, 1);
+      const int64_t* total_dev = offsets_[h].data_ptr<int64_t>() + rc;
       hipLaunchKernelGGL(d_insert_kernel, dim3(grid_for(ec)), dim3(kBlock),
                          0, stream, t, nbrs_[h].data_ptr<int64_t>(),
-                         total_dev.data_ptr<int64_t>(), ec);
+                         total_dev, ec, slot_[h].data_ptr<int32_t>());
       hipLaunchKernelGGL(d_flag_kernel, dim3(grid_for(ec)), dim3(kBlock), 0,
-                         stream, t, nbrs_[h].data_ptr<int64_t>(),
-                         total_dev.data_ptr<int64_t>(), ec,
-                         flags_[h].data_ptr<int64_t>());
+                         stream, t, slot_[h].data_ptr<int32_t>(), total_dev,
+                         ec, flags_[h].data_ptr<int64_t>());
       auto ranks = torch::cumsum(flags_[h], 0);
       hipLaunchKernelGGL(d_assign_kernel, dim3(grid_for(ec)), dim3(kBlock),
                          0, stream, t, nbrs_[h].data_ptr<int64_t>(),
-                         total_dev.data_ptr<int64_t>(), ec,
+                         slot_[h].data_ptr<int32_t>(), total_dev, ec,
                          ranks.data_ptr<int64_t>(),
-                         flags_[h].data_ptr<int64_t>(),
-                         count_dev_.data_ptr<int64_t>(),
-                         uniq_[h].data_ptr<int64_t>(),
-                         stats_.data_ptr<int64_t>() + 1 + h);
-      hipLaunchKernelGGL(d_bump_count_kernel, dim3(1), dim3(64), 0, stream,
-                         count_dev_.data_ptr<int64_t>(),
-                         stats_.data_ptr<int64_t>() + 1 + h);
+                         flags_[h].data_ptr<int64_t>(), stats, (int)h + 1,
+                         uniq_[h].data_ptr<int64_t>(), stats + 1 + h);
       // relabel cols
       hipLaunchKernelGGL(d_relabel_kernel, dim3(grid_for(ec)), dim3(kBlock),
-                         0, stream, t, nbrs_[h].data_ptr<int64_t>(),
-                         total_dev.data_ptr<int64_t>(), ec,
-                         cols_[h].data_ptr<int64_t>());
+                         0, stream, t, slot_[h].data_ptr<int32_t>(),
+                         total_dev, ec, cols_[h].data_ptr<int64_t>());
       frontier = uniq_[h];
-      frontier_n = stats_.narrow(0, 1 + h, 1);
     }
     std::vector<torch::Tensor> eids_out;
     if (with_eid_)
@@ -391,10 +383,7 @@ class DeferredSampler {
  private:
   DTableView view() {
     DTableView t;
-    t.keys = reinterpret_cast<uint64_t*>(keys_.data_ptr());
-    t.first_idx =
-        reinterpret_cast<unsigned long long*>(first_idx_.data_ptr());
-    t.local_id = local_id_.data_ptr<int64_t>();
+    t.slots = reinterpret_cast<DSlot*>(table_.data_ptr());
     t.mask = (uint64_t)table_cap_ - 1;
     return t;
   }
@@ -403,10 +392,10 @@ class DeferredSampler {
   bool with_eid_;
   torch::Device device_;
   int64_t table_cap_ = 0, total_node_cap_ = 0;
-  torch::Tensor keys_, first_idx_, local_id_, count_dev_;
-  torch::Tensor seed_uniq_, seed_flags_, seed_n_, stats_;
+  torch::Tensor table_;
+  torch::Tensor seed_uniq_, seed_flags_, seed_slot_, seed_n_, stats_;
   std::vector<torch::Tensor> counts_, offsets_, nbrs_, eids_, rows_, cols_,
-      uniq_, flags_;
+      uniq_, flags_, slot_;
 };
 
 std::shared_ptr<DeferredSampler> deferred_sampler_create(

@@ -43,6 +43,9 @@
 #include <hip/hip_bf16.h>
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include <cstdlib>
+#include <cstring>
+
 #include "hip_common.h"
 #include "../include/common.h"
 
@@ -306,15 +309,17 @@ __device__ __forceinline__ int64_t wave_uniform(int64_t v) {
 // src_off[k] = first position i of the sorted keys with key[i] >= k (and
 // n_edge past the last key): position i fills k in (key[i-1], key[i]], the
 // head [0, key[0]] and the tail (key[E-1], n_src] are spread over the grid.
-// No atomics, no cumsum.  Keys outside [0, n_src) break the caller's
-// contract; they are clamped so that no store leaves src_off.
+// No atomics, no cumsum.  Keys are clamped to [-1, n_src] so that no store
+// leaves src_off[0 .. n_src]: a key >= n_src counts as n_src, which is what
+// "first i with key[i] >= k" says for every k <= n_src (segment_offsets
+// relies on it for targets past n_tgt); a negative key as -1.
 __global__ void seg_boundary_kernel(const int64_t* __restrict__ key,
                                     int64_t n_edge, int64_t n_src,
                                     int64_t* __restrict__ src_off) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t g0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   auto clamped = [n_src](int64_t k) {
-    return k < 0 ? (int64_t)-1 : (k < n_src ? k : n_src - 1);
+    return k < 0 ? (int64_t)-1 : (k < n_src ? k : n_src);
   };
   const int64_t first = clamped(key[0]), last = clamped(key[n_edge - 1]);
   for (int64_t k = g0; k <= first; k += stride) src_off[k] = 0;
@@ -323,6 +328,124 @@ __global__ void seg_boundary_kernel(const int64_t* __restrict__ key,
   for (int64_t i = 1 + g0; i < n_edge; i += stride) {
     const int64_t hi = clamped(key[i]);
     for (int64_t k = clamped(key[i - 1]) + 1; k <= hi; ++k) src_off[k] = i;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The inverted index as a counting sort (hip_segment_transpose).  A batch
+// has a mean in-degree near 1, so almost every list has 0 or 1 entries and
+// a full sort of E keys orders next to nothing.  Five steps, a launch each:
+//   zero    cnt[0 .. n_src]
+//   count   slot[e] = cnt[col[e] + 1]++   (integer atomics: the counts do
+//           not depend on the order, only which entry gets which slot does)
+//   scan    src_off = inclusive cumsum(cnt), so src_off[s] = #{col < s}
+//   fill    tmp[src_off[col[e]] + slot[e]] = e
+//   order   each list of tmp, ranked ascending, goes to in_edge (as tgt[e]
+//           when tgt is given): the output no longer depends on the slots.
+// A col outside [0, n_src) breaks the caller's contract; it is clamped into
+// the range so that no access leaves the buffers and every entry of
+// in_edge is written.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int64_t seg_clamp_src(int64_t s, int64_t n_src) {
+  return s < 0 ? 0 : (s < n_src ? s : n_src - 1);
+}
+
+__global__ void seg_index_zero_kernel(unsigned long long* __restrict__ cnt,
+                                      int64_t n) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    cnt[i] = 0;
+}
+
+__global__ void seg_index_count_kernel(const int64_t* __restrict__ col,
+                                       int64_t n_edge, int64_t n_src,
+                                       unsigned long long* __restrict__ cnt,
+                                       int64_t* __restrict__ slot) {
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+       e < n_edge; e += (int64_t)gridDim.x * blockDim.x)
+    slot[e] = (int64_t)atomicAdd(&cnt[seg_clamp_src(col[e], n_src) + 1], 1ull);
+}
+
+__global__ void seg_index_fill_kernel(const int64_t* __restrict__ col,
+                                      int64_t n_edge, int64_t n_src,
+                                      const int64_t* __restrict__ src_off,
+                                      const int64_t* __restrict__ slot,
+                                      int64_t* __restrict__ tmp) {
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+       e < n_edge; e += (int64_t)gridDim.x * blockDim.x)
+    tmp[src_off[seg_clamp_src(col[e], n_src)] + slot[e]] = e;
+}
+
+// One lane per source, 64 consecutive sources per wave; a rank sort out of
+// place: the entries are distinct edge positions, so the rank of v, the
+// number of entries below it, is its place.  A list of up to kLaneList
+// entries (nearly all of them) is ranked by its own lane in registers.
+// Longer lists are taken one after the other by the whole wave: the list is
+// read in chunks of 64, one entry per lane, and each lane compares its own
+// entries with the chunk through lane reads, so a list of n entries costs
+// ceil(n / 64)^2 * 64 read-and-compare steps on one wave, about 390 000
+// for n = 5000: quadratic, the price of a hub (docs/kernels.md).
+constexpr int kLaneList = 4;
+
+// lane `lane` (the same in every lane: a constant once unrolled) of v
+__device__ __forceinline__ int64_t seg_readlane64(int64_t v, int lane) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
+  const uint32_t hi =
+      (uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), lane);
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+__global__ void __launch_bounds__(kBlock)
+seg_index_order_kernel(const int64_t* __restrict__ src_off, int64_t n_src,
+                       const int64_t* __restrict__ tmp,
+                       const int64_t* __restrict__ tgt,
+                       int64_t* __restrict__ in_edge) {
+  const int lane = threadIdx.x % kWave;
+  const int64_t n_wave = (int64_t)gridDim.x * (kBlock / kWave);
+  const int64_t n_group = (n_src + kWave - 1) / kWave;
+  for (int64_t g = blockIdx.x * (int64_t)(kBlock / kWave) +
+                   threadIdx.x / kWave;
+       g < n_group; g += n_wave) {
+    const int64_t s = g * kWave + lane;
+    int64_t lo = 0, len = 0;
+    if (s < n_src) {
+      lo = src_off[s];
+      len = src_off[s + 1] - lo;
+    }
+    if (len >= 1 && len <= kLaneList) {
+      // all loads of the list in flight at once, ranked in registers
+      int64_t v[kLaneList];
+#pragma unroll
+      for (int i = 0; i < kLaneList; ++i)
+        v[i] = i < len ? tmp[lo + i] : INT64_MAX;
+#pragma unroll
+      for (int i = 0; i < kLaneList; ++i) {
+        int rank = 0;
+#pragma unroll
+        for (int j = 0; j < kLaneList; ++j) rank += v[j] < v[i] ? 1 : 0;
+        if (i < len) in_edge[lo + rank] = tgt ? tgt[v[i]] : v[i];
+      }
+    }
+    unsigned long long todo = __ballot(len > kLaneList);
+    while (todo) {
+      const int owner = __ffsll(todo) - 1;
+      todo &= todo - 1;
+      const int64_t o = __shfl(lo, owner);
+      const int64_t n = __shfl(len, owner);
+      for (int64_t i0 = 0; i0 < n; i0 += kWave) {
+        const int64_t i = i0 + lane;
+        const int64_t v = i < n ? tmp[o + i] : INT64_MAX;
+        int64_t rank = 0;
+        for (int64_t j0 = 0; j0 < n; j0 += kWave) {
+          // lanes past the list hold INT64_MAX, which is below no entry
+          const int64_t w = j0 + lane < n ? tmp[o + j0 + lane] : INT64_MAX;
+#pragma unroll
+          for (int j = 0; j < kWave; ++j)
+            rank += seg_readlane64(w, j) < v ? 1 : 0;
+        }
+        if (i < n) in_edge[o + rank] = tgt ? tgt[v] : v;
+      }
+    }
   }
 }
 
@@ -1320,27 +1443,33 @@ torch::Tensor hip_segment_mean_cat_bwd(const torch::Tensor& dy,
   return segment_mean_bwd<true>(dy, col, offsets, n_src, order_independent);
 }
 
-// Inverted index of col: (src_off int64 [n_src + 1], in_edge int64 [E]).
-// in_edge[src_off[s] : src_off[s + 1]] lists the edges e with col[e] == s
-// in ascending e (stable sort): as tgt[e] when tgt is given (what the
-// gather backward reads), as the position e otherwise.  A stable rocprim
-// radix_sort_pairs over the low ceil(log2(n_src)) key bits and one
-// boundary kernel; scratch from the caching allocator, no host sync.
-std::tuple<torch::Tensor, torch::Tensor> hip_segment_transpose(
+// CSR offsets of ascending target ids: int64 [n_tgt + 1], element k the
+// first position i with tgt[i] >= k, the last one E for tgt < n_tgt.  For
+// ascending tgt this is torch.searchsorted(tgt, arange(n_tgt + 1)) in one
+// streaming pass over tgt instead of a binary search per target.
+torch::Tensor hip_segment_offsets(const torch::Tensor& tgt, int64_t n_tgt) {
+  check_index_1d(tgt, "tgt");
+  TORCH_CHECK(n_tgt >= 0, "segment_offsets: n_tgt must be >= 0");
+  const int64_t n_edge = tgt.numel();
+  if (n_edge == 0 || n_tgt == 0)
+    return torch::zeros({n_tgt + 1}, tgt.options());
+  auto off = torch::empty({n_tgt + 1}, tgt.options());
+  hipLaunchKernelGGL(seg_boundary_kernel,
+                     dim3(grid_for(std::max(n_edge, n_tgt + 1))),
+                     dim3(kBlock), 0, current_stream(),
+                     tgt.data_ptr<int64_t>(), n_edge, n_tgt,
+                     off.data_ptr<int64_t>());
+  return off;
+}
+
+// The inverted index through a stable rocprim radix_sort_pairs over the low
+// ceil(log2(n_src)) key bits and one boundary kernel (GLT_SEGMENT_INDEX=
+// sort): what the counting sort replaced, kept for A/B runs and as the
+// second opinion of the tests.
+static std::tuple<torch::Tensor, torch::Tensor> segment_index_by_sort(
     const torch::Tensor& col, int64_t n_src,
     const c10::optional<torch::Tensor>& tgt) {
-  check_index_1d(col, "col");
   const int64_t n_edge = col.numel();
-  TORCH_CHECK(n_src >= 0, "segment_transpose: n_src must be >= 0");
-  if (tgt.has_value()) {
-    check_index_1d(*tgt, "tgt");
-    TORCH_CHECK(tgt->numel() == n_edge,
-                "segment_transpose: tgt must have one entry per edge");
-  }
-  if (n_edge == 0)
-    return {torch::zeros({n_src + 1}, col.options()),
-            torch::empty({0}, col.options())};
-  TORCH_CHECK(n_src > 0, "segment_transpose: edges but no source rows");
   auto src_off = torch::empty({n_src + 1}, col.options());
   auto in_edge = torch::empty({n_edge}, col.options());
   auto keys = torch::empty({n_edge}, col.options());
@@ -1366,6 +1495,65 @@ std::tuple<torch::Tensor, torch::Tensor> hip_segment_transpose(
                      dim3(kBlock), 0, stream, keys.data_ptr<int64_t>(),
                      n_edge, n_src, src_off.data_ptr<int64_t>());
   return {src_off, in_edge};
+}
+
+// The inverted index as a counting sort (kernels and steps above);
+// scratch from the caching allocator, no host sync.
+static std::tuple<torch::Tensor, torch::Tensor> segment_index_by_count(
+    const torch::Tensor& col, int64_t n_src,
+    const c10::optional<torch::Tensor>& tgt) {
+  const int64_t n_edge = col.numel();
+  auto cnt = torch::empty({n_src + 1}, col.options());
+  auto slot = torch::empty({n_edge}, col.options());
+  auto tmp = torch::empty({n_edge}, col.options());
+  auto in_edge = torch::empty({n_edge}, col.options());
+  auto* cntp = reinterpret_cast<unsigned long long*>(cnt.data_ptr());
+  const int64_t* colp = col.data_ptr<int64_t>();
+  hipStream_t stream = current_stream();
+  hipLaunchKernelGGL(seg_index_zero_kernel, dim3(grid_for(n_src + 1)),
+                     dim3(kBlock), 0, stream, cntp, n_src + 1);
+  hipLaunchKernelGGL(seg_index_count_kernel, dim3(grid_for(n_edge)),
+                     dim3(kBlock), 0, stream, colp, n_edge, n_src, cntp,
+                     slot.data_ptr<int64_t>());
+  auto src_off = torch::cumsum(cnt, 0);
+  hipLaunchKernelGGL(seg_index_fill_kernel, dim3(grid_for(n_edge)),
+                     dim3(kBlock), 0, stream, colp, n_edge, n_src,
+                     src_off.data_ptr<int64_t>(), slot.data_ptr<int64_t>(),
+                     tmp.data_ptr<int64_t>());
+  hipLaunchKernelGGL(seg_index_order_kernel,
+                     dim3(wave_grid((n_src + kWave - 1) / kWave)),
+                     dim3(kBlock), 0, stream, src_off.data_ptr<int64_t>(),
+                     n_src, tmp.data_ptr<int64_t>(),
+                     tgt.has_value() ? tgt->data_ptr<int64_t>() : nullptr,
+                     in_edge.data_ptr<int64_t>());
+  return {src_off, in_edge};
+}
+
+// Inverted index of col: (src_off int64 [n_src + 1], in_edge int64 [E]).
+// in_edge[src_off[s] : src_off[s + 1]] lists the edges e with col[e] == s
+// in ascending e: as tgt[e] when tgt is given (what the gather backward
+// reads), as the position e otherwise.  A counting sort by default, the
+// rocprim sort with GLT_SEGMENT_INDEX=sort (read at every call); both give
+// the same tensors.
+std::tuple<torch::Tensor, torch::Tensor> hip_segment_transpose(
+    const torch::Tensor& col, int64_t n_src,
+    const c10::optional<torch::Tensor>& tgt) {
+  check_index_1d(col, "col");
+  const int64_t n_edge = col.numel();
+  TORCH_CHECK(n_src >= 0, "segment_transpose: n_src must be >= 0");
+  if (tgt.has_value()) {
+    check_index_1d(*tgt, "tgt");
+    TORCH_CHECK(tgt->numel() == n_edge,
+                "segment_transpose: tgt must have one entry per edge");
+  }
+  if (n_edge == 0)
+    return {torch::zeros({n_src + 1}, col.options()),
+            torch::empty({0}, col.options())};
+  TORCH_CHECK(n_src > 0, "segment_transpose: edges but no source rows");
+  const char* mode = std::getenv("GLT_SEGMENT_INDEX");
+  if (mode != nullptr && std::strcmp(mode, "sort") == 0)
+    return segment_index_by_sort(col, n_src, tgt);
+  return segment_index_by_count(col, n_src, tgt);
 }
 
 torch::Tensor hip_segment_mean_bwd_gather(

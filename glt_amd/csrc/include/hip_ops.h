@@ -129,10 +129,15 @@ torch::Tensor hip_segment_mean_cat_bwd(const torch::Tensor& dy,
                                        int64_t n_src,
                                        bool order_independent = false);
 
+// CSR offsets int64 [n_tgt + 1] of ascending target ids: element k is the
+// first i with tgt[i] >= k (torch.searchsorted(tgt, arange(n_tgt + 1))).
+torch::Tensor hip_segment_offsets(const torch::Tensor& tgt, int64_t n_tgt);
+
 // Atomic-free backward of the two above.  hip_segment_transpose builds the
 // inverted index of col: in_edge[src_off[s] : src_off[s + 1]] lists the
 // edges with col[e] == s in ascending e, as tgt[e] when tgt is given (the
-// form the gather backward takes) and as e otherwise.  The gather backward
+// form the gather backward takes) and as e otherwise; a counting sort, or
+// the rocprim sort with GLT_SEGMENT_INDEX=sort.  The gather backward
 // sums per source row in fp32 and returns dx [n_src, F] in dy's dtype,
 // every row written; mask ([>= n_src, F], dy's dtype) applies
 // threshold_backward(dx, mask, 0) in the same pass.

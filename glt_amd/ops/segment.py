@@ -47,7 +47,12 @@ def _boundaries(n: int, device) -> torch.Tensor:
 
 
 def _offsets(tgt: torch.Tensor, n_tgt: int) -> torch.Tensor:
-    """CSR offsets [n_tgt + 1] of the ascending target ids."""
+    """CSR offsets [n_tgt + 1] of the ascending target ids: one streaming
+    pass on the device, a binary search per target on the CPU."""
+    if tgt.is_cuda and tgt.dtype == torch.int64:
+        from .. import _C
+
+        return _C.segment_offsets(tgt.contiguous(), n_tgt)
     return torch.searchsorted(tgt, _boundaries(n_tgt, tgt.device))
 
 
