@@ -19,6 +19,8 @@ def main():
     ap.add_argument("--split-ratio", type=float, default=1.0)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--dtype", type=str, default="float32")
+    ap.add_argument("--quantize", choices=["int8", "fp8"], default=None,
+                    help="store 8-bit rows; lookups return bf16")
     args = ap.parse_args()
 
     import glt_amd
@@ -27,7 +29,8 @@ def main():
     assert torch.cuda.is_available(), "GPU micro-benchmark"
     dtype = getattr(torch, args.dtype)
     feats = torch.randn(args.rows, args.dim).to(dtype)
-    f = Feature(feats, split_ratio=args.split_ratio, device=0, with_gpu=True)
+    f = Feature(feats, split_ratio=args.split_ratio, device=0, with_gpu=True,
+                quantize=args.quantize)
     f.lazy_init()
     ids = torch.randint(0, args.rows, (args.batch,), device="cuda")
     for _ in range(3):
@@ -38,13 +41,16 @@ def main():
         out = f[ids]
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    bytes_moved = args.iters * args.batch * args.dim * out.element_size() * 2
+    # stored row read + output row written
+    bytes_moved = args.iters * args.batch * (
+        f.storage_bytes_per_row + args.dim * out.element_size())
     print(json.dumps({
         "metric": "feature_gather_GBps",
         "value": round(bytes_moved / dt / 1e9, 2),
         "split_ratio": args.split_ratio,
         "rows_per_sec_M": round(args.iters * args.batch / dt / 1e6, 2),
         "dtype": args.dtype,
+        "quantize": args.quantize,
         "dim": args.dim,
     }))
 

@@ -141,6 +141,19 @@ struct FeatureStorePy {
   int64_t dim() { return ufs_dim(p.get()); }
 };
 
+struct QuantFeatureStorePy {
+  std::shared_ptr<QuantFeatureStore> p;
+  QuantFeatureStorePy(int64_t device, int64_t dim, const std::string& fmt)
+      : p(qfs_create(device, dim, fmt)) {}
+  void append(const torch::Tensor& seg) { qfs_append(p.get(), seg); }
+  torch::Tensor gather(const torch::Tensor& rows,
+                       torch::ScalarType out_dtype) {
+    return qfs_gather(p.get(), rows, out_dtype);
+  }
+  int64_t rows() { return qfs_rows(p.get()); }
+  int64_t dim() { return qfs_dim(p.get()); }
+};
+
 torch::Tensor ipc_open_py(const std::string& handle, int64_t device,
                           const std::vector<int64_t>& shape,
                           int64_t dtype_code) {
@@ -289,6 +302,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("gather", &FeatureStorePy::gather)
       .def("rows", &FeatureStorePy::rows)
       .def("dim", &FeatureStorePy::dim);
+
+  m.def("quantize_rows", &hip_quantize_rows, py::arg("x"), py::arg("fmt"));
+  py::class_<QuantFeatureStorePy>(m, "QuantFeatureStore")
+      .def(py::init<int64_t, int64_t, const std::string&>(),
+           py::arg("device"), py::arg("dim"), py::arg("fmt"))
+      .def("append", &QuantFeatureStorePy::append)
+      .def("gather", &QuantFeatureStorePy::gather, py::arg("rows"),
+           py::arg("out_dtype"))
+      .def("rows", &QuantFeatureStorePy::rows)
+      .def("dim", &QuantFeatureStorePy::dim);
 
   m.def("sage_gemm", &hip_sage_gemm, py::arg("A"), py::arg("B"),
         py::arg("bias") = py::none(), py::arg("relu") = false);

@@ -14,21 +14,13 @@
  * per call, XCD-friendly grid-stride.
  */
 #include "hip_common.h"
+#include "hip_seg_table.h"
 #include "../include/common.h"
 #include "../include/hip_ops.h"
 
 namespace glt {
 
 namespace {
-
-constexpr int kMaxSegs = 16;
-
-struct SegTable {
-  const char* base[kMaxSegs];
-  int64_t row_start[kMaxSegs + 1];  // ascending; row r in seg s iff
-                                    // row_start[s] <= r < row_start[s+1]
-  int n;
-};
 
 // Element-level gather: thread t copies VEC bytes of slot (t % slots) of
 // output row (t / slots).  Full lane utilization for short feature rows
@@ -46,9 +38,7 @@ __global__ void gather_rows_kernel(SegTable segs, int64_t row_bytes,
     const int64_t i = idx / slots;
     const int64_t j = idx - i * slots;
     const int64_t r = rows[i];
-    int s = 0;
-    while (s + 1 < segs.n && r >= segs.row_start[s + 1]) ++s;
-    const char* src = segs.base[s] + (r - segs.row_start[s]) * row_bytes;
+    const char* src = seg_row(segs, r, row_bytes);
     char* dst = out + i * row_bytes;
     if (VEC == 16) {
       reinterpret_cast<uint4*>(dst)[j] =
@@ -98,15 +88,7 @@ class UnifiedFeatureStore {
         torch::TensorOptions().dtype(dtype_).device(device_));
     if (n == 0) return out;
 
-    SegTable t;
-    t.n = (int)segs_.size();
-    int64_t acc = 0;
-    for (int i = 0; i < t.n; ++i) {
-      t.base[i] = reinterpret_cast<const char*>(segs_[i].data_ptr());
-      t.row_start[i] = acc;
-      acc += segs_[i].size(0);
-    }
-    t.row_start[t.n] = acc;
+    const SegTable t = make_seg_table(segs_);
 
     const int64_t row_bytes = dim_ * (int64_t)elementSize(dtype_);
     const int64_t vec = row_bytes % 16 == 0 ? 16

@@ -389,4 +389,23 @@ torch::Tensor ufs_gather(UnifiedFeatureStore* s, const torch::Tensor& rows);
 int64_t ufs_rows(UnifiedFeatureStore* s);
 int64_t ufs_dim(UnifiedFeatureStore* s);
 
+// --- 8-bit feature rows (hip_quant_feature.hip) -----------------------------
+// Packed table: uint8 [N, S], S = round_up(F + 4, 16); a row is F codes,
+// zero padding and its fp32 scale in the last four bytes.  fmt is 'int8'
+// (symmetric, |code| <= 127) or 'fp8' (OCP e4m3).  x: contiguous 2-D device
+// tensor of fp32, bf16 or fp16.  All arguments are validated before a launch.
+torch::Tensor hip_quantize_rows(const torch::Tensor& x,
+                                const std::string& fmt);
+// UnifiedFeatureStore over packed segments of one dim and fmt; gather
+// dequantises into fp32 or bf16 rows [n, dim] in the same pass.
+class QuantFeatureStore;
+std::shared_ptr<QuantFeatureStore> qfs_create(int64_t device_index,
+                                              int64_t dim,
+                                              const std::string& fmt);
+void qfs_append(QuantFeatureStore* s, const torch::Tensor& seg);
+torch::Tensor qfs_gather(QuantFeatureStore* s, const torch::Tensor& rows,
+                         torch::ScalarType out_dtype);
+int64_t qfs_rows(QuantFeatureStore* s);
+int64_t qfs_dim(QuantFeatureStore* s);
+
 }  // namespace glt

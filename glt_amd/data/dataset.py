@@ -66,12 +66,15 @@ class Dataset:
                            device_group_list: Optional[List[DeviceGroup]] = None,
                            device: Optional[int] = None,
                            with_gpu: bool = True,
-                           dtype: Optional[torch.dtype] = None):
+                           dtype: Optional[torch.dtype] = None,
+                           quantize: Optional[str] = None,
+                           dequant_dtype: torch.dtype = torch.bfloat16):
         def build(feat, topo, i2i):
             if sort_func is not None and topo is not None and i2i is None:
                 feat, i2i = sort_func(feat, split_ratio, topo)
             return Feature(feat, split_ratio, device_group_list, device,
-                           with_gpu, dtype=dtype, id2index=i2i)
+                           with_gpu, dtype=dtype, id2index=i2i,
+                           quantize=quantize, dequant_dtype=dequant_dtype)
 
         if isinstance(node_feature_data, dict):
             self.node_features = {}
@@ -93,18 +96,22 @@ class Dataset:
                            split_ratio: float = 0.0,
                            device_group_list=None, device=None,
                            with_gpu: bool = True,
-                           dtype: Optional[torch.dtype] = None):
+                           dtype: Optional[torch.dtype] = None,
+                           quantize: Optional[str] = None,
+                           dequant_dtype: torch.dtype = torch.bfloat16):
         if isinstance(edge_feature_data, dict):
             self.edge_features = {}
             for etype, feat in edge_feature_data.items():
                 i2i = id2idx.get(etype) if isinstance(id2idx, dict) else None
                 self.edge_features[etype] = Feature(
                     feat, split_ratio, device_group_list, device, with_gpu,
-                    dtype=dtype, id2index=i2i)
+                    dtype=dtype, id2index=i2i, quantize=quantize,
+                    dequant_dtype=dequant_dtype)
         elif edge_feature_data is not None:
             self.edge_features = Feature(
                 edge_feature_data, split_ratio, device_group_list, device,
-                with_gpu, dtype=dtype, id2index=id2idx)
+                with_gpu, dtype=dtype, id2index=id2idx, quantize=quantize,
+                dequant_dtype=dequant_dtype)
         return self
 
     def init_node_labels(self, node_label_data=None):

@@ -45,6 +45,12 @@ class Feature:
       dtype: optional cast.
       id2index: optional [max_id+1] map from global ids to row positions
         (set when features were reordered or cached).
+      quantize: None, 'int8' or 'fp8'.  When set, the table is packed once
+        into 8-bit rows with an inline per-row fp32 scale (ops/quant.py:
+        uint8 [N, round_up(F + 4, 16)]) and the original is dropped; both
+        tiers hold packed rows and lookups dequantise in the gather kernel.
+      dequant_dtype: dtype of the rows a quantised Feature returns
+        (torch.bfloat16 or torch.float32).
     """
 
     def __init__(self, feature_tensor: torch.Tensor,
@@ -52,10 +58,20 @@ class Feature:
                  device_group_list: Optional[List[DeviceGroup]] = None,
                  device: Optional[int] = None, with_gpu: bool = True,
                  dtype: Optional[torch.dtype] = None,
-                 id2index: Optional[torch.Tensor] = None):
+                 id2index: Optional[torch.Tensor] = None,
+                 quantize: Optional[str] = None,
+                 dequant_dtype: torch.dtype = torch.bfloat16):
         assert feature_tensor.dim() == 2
         if dtype is not None and feature_tensor.dtype != dtype:
             feature_tensor = feature_tensor.to(dtype)
+        self.quantize = quantize
+        self.dequant_dtype = dequant_dtype
+        self._dim = feature_tensor.size(1)  # logical F
+        if quantize is not None:
+            from ..ops.quant import quantize_rows_cpu
+            assert dequant_dtype in (torch.bfloat16, torch.float32)
+            feature_tensor = quantize_rows_cpu(feature_tensor.cpu(),
+                                               quantize)
         self.cpu_tensor = feature_tensor.contiguous()
         # split_ratio='auto': size the HBM-resident hot tier from free HBM
         # at lazy-init time (288 GB/GPU usually fits everything; cap at 80%
@@ -86,12 +102,11 @@ class Feature:
         n = self.cpu_tensor.size(0)
         if self._auto_split:
             free_b, _ = torch.cuda.mem_get_info(dev)
-            row_bytes = self.cpu_tensor.size(1) * \
-                self.cpu_tensor.element_size()
+            row_bytes = self.storage_bytes_per_row
             self.split_ratio = min(
                 1.0, (free_b * 0.8) / max(row_bytes * n, 1))
         hot = int(n * min(max(self.split_ratio, 0.0), 1.0))
-        store = _C.UnifiedFeatureStore(dev)
+        store = self._new_store(dev)
         groups = self.device_group_list
         if hot > 0:
             if groups:
@@ -131,6 +146,12 @@ class Feature:
         self._store = store
         self._device_rows = hot
 
+    def _new_store(self, dev):
+        from .. import _C
+        if self.quantize is not None:
+            return _C.QuantFeatureStore(dev, self._dim, self.quantize)
+        return _C.UnifiedFeatureStore(dev)
+
     # -- lookups ------------------------------------------------------------
     def _id2index_on(self, device) -> torch.Tensor:
         """Device-resident id2index, cached per device — converting per
@@ -154,26 +175,46 @@ class Feature:
             dev = self.device if self.device is not None else \
                 torch.cuda.current_device()
             rows = rows.to(torch.device("cuda", dev), non_blocking=True)
+            if self.quantize is not None:
+                return self._store.gather(rows, self.dequant_dtype)
             return self._store.gather(rows)
-        return self.cpu_tensor[rows.cpu()]
+        return self._host_rows(rows.cpu())
+
+    def _host_rows(self, rows: torch.Tensor) -> torch.Tensor:
+        """Host lookup; a quantised table is dequantised to the same bits
+        as the device path."""
+        out = self.cpu_tensor[rows]
+        if self.quantize is not None:
+            from ..ops.quant import dequantize_rows
+            out = dequantize_rows(out, self._dim, self.quantize,
+                                  self.dequant_dtype)
+        return out
 
     def cpu_get(self, ids: torch.Tensor) -> torch.Tensor:
         """Host-side lookup (serves remote RPC feature requests)."""
         rows = ids.long().cpu()
         if self.id2index is not None:
             rows = self.id2index.cpu()[rows]
-        return self.cpu_tensor[rows]
+        return self._host_rows(rows)
 
     @property
     def shape(self):
-        return self.cpu_tensor.shape
+        return torch.Size((self.cpu_tensor.size(0), self._dim))
 
     def size(self, dim: int):
-        return self.cpu_tensor.size(dim)
+        return self.shape[dim]
 
     @property
     def dtype(self):
+        if self.quantize is not None:
+            return self.dequant_dtype
         return self.cpu_tensor.dtype
+
+    @property
+    def storage_bytes_per_row(self):
+        """Bytes a stored row takes in either tier (the packed stride of a
+        quantised table)."""
+        return self.cpu_tensor.size(1) * self.cpu_tensor.element_size()
 
     @property
     def device_rows(self):
@@ -198,14 +239,17 @@ class Feature:
             dev_segments = list(getattr(self, "_keepalive", []) or [])
         return (self.cpu_tensor, self.split_ratio, self.device_group_list,
                 self.device, self.with_gpu, self.id2index, dev_segments,
-                self._device_rows)
+                self._device_rows, self.quantize, self.dequant_dtype,
+                self._dim)
 
     @classmethod
     def from_ipc(cls, handle):
         (cpu_tensor, split_ratio, groups, device, with_gpu, id2index,
-         dev_segments, device_rows) = handle
+         dev_segments, device_rows, quantize, dequant_dtype, dim) = handle
+        # a quantised table arrives packed and is taken as it is
         f = cls(cpu_tensor, split_ratio, groups, device, with_gpu,
                 id2index=id2index)
+        f.quantize, f.dequant_dtype, f._dim = quantize, dequant_dtype, dim
         if dev_segments:
             f._ipc_segments = dev_segments
             f._ipc_device_rows = device_rows
@@ -220,7 +264,7 @@ class Feature:
 
         dev = self.device if self.device is not None else \
             torch.cuda.current_device()
-        store = _C.UnifiedFeatureStore(dev)
+        store = self._new_store(dev)
         for seg in segs:
             if seg.device.index != dev:
                 _C.enable_peer_access(dev, seg.device.index)

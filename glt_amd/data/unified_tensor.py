@@ -10,13 +10,23 @@ import torch
 
 
 class UnifiedTensor:
-    def __init__(self, device: int, dtype: torch.dtype = torch.float32):
+    """With quantize='int8' or 'fp8', `dim` is the logical row width, the
+    appended tensors are packed rows (ops.quantize_rows) and lookups return
+    dequantised rows of `dtype` (bf16 or fp32)."""
+
+    def __init__(self, device: int, dtype: torch.dtype = torch.float32,
+                 quantize: Optional[str] = None, dim: Optional[int] = None):
         from .. import _C
 
         self._C = _C
         self.device = device
         self.dtype = dtype
-        self._store = _C.UnifiedFeatureStore(device)
+        self.quantize = quantize
+        if quantize is not None:
+            assert dim is not None, "a quantised UnifiedTensor needs dim="
+            self._store = _C.QuantFeatureStore(device, dim, quantize)
+        else:
+            self._store = _C.UnifiedFeatureStore(device)
         self._keepalive: List[torch.Tensor] = []
 
     def append_device_tensor(self, t: torch.Tensor):
@@ -31,8 +41,10 @@ class UnifiedTensor:
         self._keepalive += [t, mapped]
 
     def __getitem__(self, ids: torch.Tensor) -> torch.Tensor:
-        return self._store.gather(
-            ids.to(torch.device("cuda", self.device), non_blocking=True))
+        rows = ids.to(torch.device("cuda", self.device), non_blocking=True)
+        if self.quantize is not None:
+            return self._store.gather(rows, self.dtype)
+        return self._store.gather(rows)
 
     @property
     def shape(self):

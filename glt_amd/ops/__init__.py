@@ -9,6 +9,8 @@ from .relation import relation_linear, relation_linear_uses_kernel
 from .attention import (transformer_attention,
                         transformer_attention_composition,
                         transformer_attention_fused_ok)
+from .quant import (dequantize_rows, packed_stride, quantize_rows,
+                    quantize_rows_cpu)
 
 __all__ = ["segment_mean", "segment_mean_cat", "segment_weighted_sum",
            "segment_max", "segment_min", "segment_max_cat",
@@ -19,4 +21,5 @@ __all__ = ["segment_mean", "segment_mean_cat", "segment_weighted_sum",
            "gatv2_softmax_aggregate", "gatv2_composition",
            "relation_linear", "relation_linear_uses_kernel",
            "transformer_attention", "transformer_attention_composition",
-           "transformer_attention_fused_ok"]
+           "transformer_attention_fused_ok", "quantize_rows",
+           "quantize_rows_cpu", "dequantize_rows", "packed_stride"]

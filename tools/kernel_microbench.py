@@ -329,6 +329,84 @@ def tconv_table(device, iters, warmup, rounds=5):
                   f" every fused round faster: {max(tf) < min(tc)}")
 
 
+def quant_table(op, device, iters, warmup, fmt, out_dtype, tier, rounds=3):
+    """--op quantize_rows: the row quantiser at 1M x 100 and 1M x 256, fp32
+    input, us per call against the bytes moved (input row + packed row).
+
+    --op gather_dequant: QuantFeatureStore.gather of 1M random rows out of
+    a 1M-row packed table against UnifiedFeatureStore.gather of the same
+    rows from the fp32 and the bf16 table, dim 100 and 256, with the table
+    all in HBM (--tier hbm) or all in mapped pinned host memory (--tier
+    host).  The three are timed alternately, `rounds` times `iters` calls
+    each, from device events; every round is printed, with the effective
+    bytes of a call (stored row read + output row written)."""
+    from glt_amd import _C
+    from glt_amd.ops import packed_stride
+
+    def timed(fn):
+        a = torch.cuda.Event(enable_timing=True)
+        b = torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e3 / iters
+
+    def report(label, ts, nbytes):
+        med = sorted(ts)[len(ts) // 2]
+        print(f"{label}: {med:.1f} us [{' '.join('%.1f' % t for t in ts)}]"
+              f" {nbytes / 1e6:.1f} MB, {nbytes / med / 1e6:.3f} TB/s")
+
+    torch.manual_seed(0)
+    n = 1_000_000
+    odt = torch.bfloat16 if out_dtype == "bf16" else torch.float32
+    for dim in (100, 256):
+        S = packed_stride(dim)
+        x = torch.randn(n, dim, device=device)
+        if op == "quantize_rows":
+            fn = lambda: _C.quantize_rows(x, fmt)
+            for _ in range(warmup):
+                fn()
+            report(f"quantize_rows {fmt} fp32 1M x {dim}",
+                   [timed(fn) for _ in range(rounds)], n * (dim * 4 + S))
+            continue
+        rows = torch.randint(0, n, (n,), device=device)
+        tables = {"fp32": x, "bf16": x.to(torch.bfloat16),
+                  fmt: _C.quantize_rows(x, fmt)}
+        keep, fns, nbytes = [], {}, {}
+        for name, t in tables.items():
+            if tier == "host":
+                h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+                h.copy_(t)
+                keep.append(h)
+                t = _C.host_mapped_view(h, device.index)
+            if name == fmt:
+                store = _C.QuantFeatureStore(device.index, dim, fmt)
+                store.append(t)
+                fns[name] = lambda s=store: s.gather(rows, odt)
+                nbytes[name] = n * (S + dim * (2 if odt == torch.bfloat16
+                                               else 4))
+            else:
+                store = _C.UnifiedFeatureStore(device.index)
+                store.append(t)
+                fns[name] = lambda s=store: s.gather(rows)
+                nbytes[name] = 2 * n * dim * t.element_size()
+            keep.append(t)
+        for fn in fns.values():
+            for _ in range(warmup):
+                fn()
+        ts = {name: [] for name in fns}
+        for _ in range(rounds):
+            for name, fn in fns.items():
+                ts[name].append(timed(fn))
+        for name in fns:
+            what = (f"dequant to {out_dtype}" if name == fmt else "copy")
+            report(f"gather {tier} dim {dim} {name} {what}", ts[name],
+                   nbytes[name])
+
+
 # One layer of `bench_hetero.py --model rsage --dtype bf16` (1M papers, batch
 # 512, fanout 10,5, 4 relations; layer 0: K = 128, N = 256): rows per node type and, per
 # segment, (type, rows).  Every relation's aggregate covers all rows of its
@@ -423,7 +501,14 @@ def main():
                              "gcn_conv_composite", "seg_max", "seg_max_cat",
                              "sage_conv_max", "sage_conv_max_composite",
                              "seg_bwd", "gatv2", "relation_linear",
-                             "tconv"])
+                             "tconv", "quantize_rows", "gather_dequant"])
+    ap.add_argument("--fmt", choices=["int8", "fp8"], default="int8",
+                    help="quantize_rows, gather_dequant: code format")
+    ap.add_argument("--out-dtype", choices=["bf16", "fp32"], default="bf16",
+                    help="gather_dequant: dtype of the dequantised rows")
+    ap.add_argument("--tier", choices=["hbm", "host"], default="hbm",
+                    help="gather_dequant: table all in HBM or all in "
+                         "mapped pinned host memory")
     ap.add_argument("--bf16", action="store_true",
                     help="gcn_conv, seg_mean, seg_max and sage_conv_max "
                          "ops: bf16 input at F=100 (default fp32 at F=256)")
@@ -449,6 +534,10 @@ def main():
         return
     if args.op == "tconv":
         tconv_table(device, args.iters, args.warmup)
+        return
+    if args.op in ("quantize_rows", "gather_dequant"):
+        quant_table(args.op, device, args.iters, args.warmup, args.fmt,
+                    args.out_dtype, args.tier)
         return
     inp = build_flagship_shapes(args.op, device, args.bf16)
 
